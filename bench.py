@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- stereo Msamples/s mastered on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: started by a launcher (RANK / WORLD_SIZE / LOCAL_RANK in the environment) every
@@ -23,6 +23,13 @@ Workloads (BASELINE.json configs):
 With N ranks every rank masters its own pairs (pairs are independent: no data-path collective, weak
 scaling); the FIR tables are all-gathered over RCCL after the timed region, the only traffic that
 crosses xGMI.
+
+A plain run sets up, warms up, times the K steps and prints the line (``value``, ``ms_per_step`` and the workload's
+description).  ``--full`` adds everything else this script measures or checks: the repeat blocks, the per-stage
+timings and rooflines, the HBM traffic counters, the clock / power probe, the side workloads, the host-to-host and
+file-to-file figures, the CPU baseline with the parity check, and at N > 1 the RCCL exchange and the N = 1 point.
+``--dump-outputs DIR`` writes what the last timed step computed (the arrays a caller of ``mgx_master`` receives) as
+``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared output for output.
 
 Rendezvous, barrier and max-reduce go through matchering_amd.ranks (a local socket: no torch anywhere in this
 file); device memory, streams and timing go through libmgx.  Prints ONE JSON line on rank 0.
@@ -52,6 +59,8 @@ KERNEL_BYTES = {"convolve": 16,    # S3: read 8 + write 8 (the mid plane's 4 B a
                 "limit": 16}       # read 8 + write 8 per launch of the one-pass limiter (S5's 24 B model
                                    # counts a second read that this kernel takes from the L2 / Infinity Cache)
 WORKLOADS = sorted(PIPELINE_BYTES)
+DUMP_BYTES = 60_000_000        # --dump-outputs: all ranks' files together stay below 64 MB
+DUMP_SEED = 20240917           # fixes which frames a sampled dump keeps
 
 
 def kernel_name(stage, fft):
@@ -73,6 +82,12 @@ def parse():
     ap.add_argument("--workload", default="auto", choices=["auto"] + WORKLOADS,
                     help="auto = 8min_full on one GPU, 4min_x8_full per rank on several (96k_16k_x16_full: config #5's "
                          "per-GPU share, sixteen 96 kHz pairs per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline figure (see the module docstring); "
+                         "a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32; a fixed, seeded sample of the "
+                         "frames where the whole output would exceed 60 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the side workloads and the PCIe figure")
     ap.add_argument("--no-traffic", action="store_true",
@@ -85,7 +100,10 @@ def parse():
                          "rank adopts its choice (batch.choose_lanes)")
     ap.add_argument("--spinup", type=float, default=0.5,
                     help="seconds of untimed steps before the warm-up (the device climbs out of its idle clocks)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.stand_in:
+        ap.error("--dump-outputs needs the GPU workload: a stand-in step computes nothing")
+    return args
 
 
 from matchering_amd.ranks import Ranks  # noqa: E402  (rendezvous + barrier + max + broadcast over a local socket)
@@ -270,6 +288,21 @@ class Workload:
         d.stage_timing(False)
         return {k: statistics.median(row[k] for row in rows) for k in rows[0] if rows[0][k] is not None}, n
 
+    def dump_outputs(self, folder, rank, world):
+        """Every pair's result as the last step left it in HBM -> ``folder/<name>.npy``, float32 (frames, 2).  Where a
+        rank's share of DUMP_BYTES cannot hold a whole result, the same seeded, sorted sample of frames is kept for a
+        given length, so that runs and builds stay comparable."""
+        os.makedirs(folder, exist_ok=True)
+        rows_max = DUMP_BYTES // world // len(self.jobs) // 8
+        what = "result" if self.want_limiter else "result_no_limiter"
+        for k, (d, t, n, r, nr, out) in enumerate(self.jobs):
+            got = d.download(out, (n, 2))
+            if n > rows_max:
+                keep = np.sort(np.random.default_rng([DUMP_SEED, n]).choice(n, rows_max, replace=False))
+                got = got[keep]
+            name = (f"rank{rank}_" if world > 1 else "") + what + (f"_pair{k}" if len(self.jobs) > 1 else "")
+            np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(got, dtype=np.float32))
+
     def release(self):
         for d, t, n, r, nr, out in self.jobs:
             for b in (t, r, out):
@@ -450,10 +483,12 @@ def run(args, ranks):
     spun = spin_up(wl.sync, wl.step, args.spinup)
     own_seconds = []
     elapsed = timed_steps(ranks, wl.sync, wl.step, args.steps, args.warmup, own_seconds)
-    # REPEAT_BLOCKS further blocks of the same K steps, each between its own two barriers: `value` stays the FIRST block
-    # (so that `steps` says what it was measured on), the spread of all of them stands beside it
+    if args.dump_outputs:
+        wl.dump_outputs(args.dump_outputs, ranks.rank, ranks.world)
+    # (--full) REPEAT_BLOCKS further blocks of the same K steps, each between its own two barriers: `value` stays the
+    # FIRST block (so that `steps` says what it was measured on), the spread of all of them stands beside it
     blocks_ms = [elapsed / args.steps * 1e3]
-    for _ in range(REPEAT_BLOCKS):
+    for _ in range(REPEAT_BLOCKS if args.full else 0):
         blocks_ms.append(timed_steps(ranks, wl.sync, wl.step, args.steps, 0) / args.steps * 1e3)
     frames_total = wl.frames * args.steps * ranks.world
     value = frames_total / elapsed / 1e6
@@ -473,10 +508,6 @@ def run(args, ranks):
 
     line.update({
         "value": round(value, 2), "ms_per_step": round(ms_per_step, 4),
-        "ms_per_step_repeats": {"min": round(min(blocks_ms), 4), "median": round(statistics.median(blocks_ms), 4),
-                                "max": round(max(blocks_ms), 4), "blocks": len(blocks_ms),
-                                "note": f"{len(blocks_ms)} blocks of {args.steps} steps each, back to back, each between two "
-                                        "barriers (maximum over ranks); the first one is `ms_per_step` / `value`"},
         "spinup": {"seconds": args.spinup, "steps": spun, "recovered_calls": getattr(spin_up, "recovered", 0),
                    "note": "untimed steps before the W warm-up steps, so that the K timed steps see a busy device rather "
                            "than the climb out of idle; no measurable effect on the boxes seen so far"},
@@ -498,10 +529,16 @@ def run(args, ranks):
                                        "all kernels (null when the profiler cannot be used)",
                                "measured_bytes": None, "measured_frac_of_8TBs": None},
     })
+    if args.full:
+        line["ms_per_step_repeats"] = {
+            "min": round(min(blocks_ms), 4), "median": round(statistics.median(blocks_ms), 4),
+            "max": round(max(blocks_ms), 4), "blocks": len(blocks_ms),
+            "note": f"{len(blocks_ms)} blocks of {args.steps} steps each, back to back, each between two "
+                    "barriers (maximum over ranks); the first one is `ms_per_step` / `value`"}
     # every rank's own time for the K steps (up to its own stream synchronisation, before the closing barrier)
     line["rank_seconds"] = [round(v, 6) for v in ranks.gather(own_seconds[0])]
 
-    # ---- multi-GPU: all-gather the FIR tables over RCCL (off the timed path) ---------------
+    # ---- multi-GPU (--full): all-gather the FIR tables over RCCL (off the timed path) ---------------
     # A failing collective is reported in the line, it does not lose the measurement -- and neither does one
     # that never returns: the exchange runs in a thread the main one waits for two minutes at most.
     exchange = {}
@@ -539,7 +576,7 @@ def run(args, ranks):
             exchange["result"] = {"ok": False, "error": str(exc)[:200]}
 
     stuck = False
-    if ranks.world > 1 and not args.stand_in:
+    if args.full and ranks.world > 1 and not args.stand_in:
         import threading
 
         worker = threading.Thread(target=exchange_fir_tables, daemon=True)
@@ -553,7 +590,7 @@ def run(args, ranks):
         line["rccl_fir_allgather"] = dict(everyone[0], ranks_ok=sum(1 for e in everyone if e.get("ok")))
         # the slowest rank's ncclCommInitRank: a box on which RCCL takes minutes to come up shows HERE, not in a timeout
         line["rccl_init_s"] = max((e.get("rccl_init_s") or 0.0) for e in everyone)
-    elif ranks.world > 1:
+    elif args.full and ranks.world > 1:
         line["rendezvous"] = {"ranks_seen": len(ranks.gather(ranks.rank)), "transport": "matchering_amd.ranks"}
         # the exchange's shape without RCCL: every rank's (fake) FIR pair, 2 x fft_size float32, gathered over the
         # rendezvous socket -- what the GPU path all-gathers over xGMI
@@ -567,7 +604,7 @@ def run(args, ranks):
                                       "ranks_ok": len(tables)}
         line["rccl_init_s"] = None
 
-    if ranks.world > 1 and not stuck:
+    if args.full and ranks.world > 1 and not stuck:
         # the SAME workload on one rank alone (the other ranks are idle, their GPUs too): the N = 1 point of a scaling
         # curve that is one workload -- the N = 1 default of this script is the 8-minute pair, another workload
         alone = Ranks(rank=0, world=1, local=ranks.local)
@@ -578,7 +615,7 @@ def run(args, ranks):
                                         "note": "rank 0 alone right after the timed region, same resident pairs and lanes; "
                                                 "value / (n_gpus x this) is the weak-scaling efficiency of ONE workload"}
         ranks.barrier()                              # (the others must not start tearing down under rank 0's run)
-    if ranks.rank == 0 and not args.stand_in and not stuck:
+    if args.full and ranks.rank == 0 and not args.stand_in and not stuck:
         # ---- rooflines of the two streaming kernels, timed where they run: inside the pipeline ----
         # (at N > 1 the other ranks are idle by now: these legs describe one GPU, as at N = 1)
         stage_ms, n0 = wl.stage_profile(max(5, min(args.steps, 20)))

@@ -287,7 +287,7 @@ def test_bench_starts_its_own_ranks_and_rccl_sees_them():
     clean = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
                           "--workload", "8min_fir_only", "--no-traffic", "--no-gpu-state", "--no-cpu-baseline",
-                          "--no-secondary", "--spinup", "0.05"], capture_output=True, text=True, timeout=600, env=clean)
+                          "--no-secondary", "--spinup", "0.05", "--full"], capture_output=True, text=True, timeout=600, env=clean)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = run.stdout.splitlines()
     assert len(lines) == 1, run.stdout[:2000]                    # the line and nothing else (RCCL's banner goes to stderr)

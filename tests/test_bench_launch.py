@@ -13,9 +13,9 @@ import pytest
 from conftest import ROOT
 
 
-def _bench(*flags, env=None, timeout=120):
+def _bench(*flags, env=None, timeout=120, full=True):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--stand-in", "--steps", "5", "--warmup", "2",
-           "--spinup", "0.01", *flags]
+           "--spinup", "0.01", *(("--full",) if full else ()), *flags]
     clean = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=dict(clean, **(env or {})))
     assert run.returncode == 0, run.stderr[-2000:]
@@ -60,6 +60,25 @@ def test_config_5_per_gpu_share_on_eight_ranks():
     assert n1["unit"] == "Msamples/s" and 0.5 < line["value"] / (8 * n1["value"]) < 1.5
     rep = line["ms_per_step_repeats"]
     assert rep["blocks"] == 6 and rep["min"] <= rep["median"] <= rep["max"] and rep["min"] <= line["ms_per_step"] <= rep["max"]
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_a_plain_run_only_times_the_steps(world):
+    """Without --full the line carries the headline figure and nothing that needs runs of its own."""
+    line = _bench("--gpus", str(world), full=False)
+    assert line["n_gpus"] == world and line["steps"] == 5 and line["warmup"] == 2
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    per_rank = line["config"]["frames_per_gpu_per_step"]
+    assert line["value"] == pytest.approx(world * per_rank * 5 / (line["ms_per_step"] * 5e-3) / 1e6, rel=1e-3)
+    for key in ("ms_per_step_repeats", "rendezvous", "rccl_fir_allgather", "n1_same_workload", "stage_ms", "roofline",
+                "cpu_baseline", "other_workloads"):
+        assert key not in line, key
+
+
+def test_outputs_are_not_dumped_from_a_stand_in():
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--stand-in", "--dump-outputs", "unused"]
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=60)
+    assert run.returncode != 0 and "--dump-outputs" in run.stderr
 
 
 def test_single_rank_needs_no_rendezvous():

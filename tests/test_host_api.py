@@ -275,6 +275,7 @@ def test_process_file_pipeline_on_cpu(tmp_path, monkeypatch):
         return out
 
     monkeypatch.setattr(core, "main", oracle_main)
+    monkeypatch.setattr(core, "_gpu", lambda: None)     # the host path, also where a GPU is visible
     codes = []
     mg.log(info_handler=lambda text: codes.append(int(str(text).split(":")[0])), show_codes=True)
     try:
@@ -486,6 +487,7 @@ def test_process_keeps_pcm_integer_end_to_end(tmp_path, monkeypatch):
         return tuple(outs)
 
     monkeypatch.setattr(core, "main", fake_main)
+    monkeypatch.setattr(core, "_gpu", lambda: None)     # the host path, also where a GPU is visible
     mg.process(str(tmp_path / "t.wav"), str(tmp_path / "r.wav"),
                [mg.pcm16(str(tmp_path / "a.wav")), mg.pcm16(str(tmp_path / "b.wav")),
                 mg.Result(str(tmp_path / "c.wav"), "PCM_24", use_limiter=False, normalize=False),
