@@ -16,8 +16,9 @@
 //  * a thread multiplies PAIRS of bins -- the lower half of its own row and their mirrors in the upper half of the
 //    mirror row -- with one fetch of the two filter values for both (conv_delay_kernel.h has the algebra: this is
 //    its Y[k], Y[N-k] without the carry);
-//  * no carry, so blocks are independent: workgroup w takes blocks w, w + G, w + 2G, ... and, having 32 registers
-//    more than the delay line, asks for the whole window of its next block a block ahead.
+//  * no carry, so blocks are independent: a workgroup takes one block per round of the grid (conv_wide_block in
+//    mgx_kernels.h) and, having 32 registers more than the delay line, asks for the whole window of its next block a
+//    block ahead.
 //
 // Window of block b (output frames [b*HOP, (b+1)*HOP), HOP = N - F): the N frames from b*HOP - F/2 on (scipy's
 // "same" centring, the filter delayed by one sample as in conv2_kernel.h); circular outputs [F, N) are the block.
@@ -87,7 +88,9 @@ struct ConvWide {
         }
     }
 
-    // ---- the row passes are the delay line's ----------------------------------------------------------------------
+    // ---- row forward -> multiply -> row back with the whole row through the LDS: the form until round 6, which
+    // k_conv_wide no longer runs.  The CPU emulation keeps it as the reference of the *_keep phases below (the two are
+    // bit-identical).  The row passes are the delay line's.
     static MGX_HD void phase_row(int tid, float2* lds) { CD::phase_row(tid, lds); }
     static MGX_HD void phase_row_back(int tid, float2* lds) { CD::phase_row_back(tid, lds); }
 
@@ -147,7 +150,7 @@ struct ConvWide {
         }
     }
 
-    // ---- the same three phases with the thread's OWN half of the row kept in registers (round 6) ---------------------
+    // ---- the same three phases with the thread's OWN half of the row kept in registers (round 6): k_conv_wide's -------
     // Row forward -> multiply -> row back moves a row through the LDS twice, but only half of it ever belongs to
     // another thread: the partner needs this row's UPPER half (the mirrors of its own lower half) and hands back the
     // products that live there.  So: the row pass stores the upper half only and keeps the lower half; the multiply

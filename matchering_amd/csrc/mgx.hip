@@ -235,7 +235,7 @@ struct mgx_handle {
         mgx_config cfg;
         float* out[3] = {nullptr, nullptr, nullptr};
     } last_call;
-    bool avoid_tail = false;                // sticky after such a report: rounds 1..K-1 as one launch each
+    bool avoid_tail = false;                // sticky after such a report: rounds 1..K-1 as one launch each (MGX_NO_TAIL=1: always)
     bool requeued = false;                  // the last check_device_error queued the call again
     // the limiter's chunks are its workgroups' numbers; after a look-back wait has expired once on this handle they are
     // drawn from an atomic ticket instead, which does not lean on the dispatch order (k_limit, mgx_kernels.h)
@@ -245,6 +245,10 @@ struct mgx_handle {
     int downloads_outstanding = 0;          // device-to-host copies queued behind them
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
+    // the paths tests compare the product against, chosen by environment switches read once at mgx_create
+    bool no_conv_wide = false;              // MGX_NO_CONV_WIDE=1: 4096 taps by k_conv<13, false> on N = 2F
+    bool no_conv_delay = false;             // MGX_NO_CONV_DELAY=1: two filter partitions by the partitioned k_conv<14, true>
+    bool fir_round4 = false;                // MGX_FIR_ROUND4=1: the dense operator at 16384 taps, the chain itself beyond
 };
 
 static int ensure(mgx_handle* h, DevBuf& b, size_t bytes) {
@@ -386,7 +390,7 @@ static int analysis_workgroups_per_cu(int log2f) {
         default: return 1;
     }
     const int by_lds = (int)((size_t)160 * 1024 / lds), by_waves = 2048 / threads;
-    return std::max(1, std::min(MGX_ANALYZE_MAX_WGS, std::min(by_lds, by_waves)));
+    return std::max(1, std::min(ANALYZE_MAX_WGS, std::min(by_lds, by_waves)));
 }
 
 template <int LOG2N>
@@ -661,15 +665,13 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(p);
     // no operator when LOWESS is not linear (robustness passes): the chain runs on the curve itself.  Otherwise the
     // dense operator up to fft_size 8192 (134 MB there, of which a product reads a sixth), its two packed factors
-    // from 16384 on (MGX_FIR_ROUND4=1: the choices of round 4, for A/B measurements)
+    // from 16384 on (h->fir_round4: the choices of round 4, dense at 16384 and the chain itself beyond)
     const bool robust = cfg->lowess_it > 0;
-    const char* env_old = std::getenv("MGX_FIR_ROUND4");
-    const bool round4 = env_old && env_old[0] == '1';            // dense at 16384, the chain itself beyond
     // (the factors are found by pushing unit vectors through the chain into two DENSE anchors x bins matrices before they
     // are packed: with lowess_delta = 0 every point of the log grid is an anchor -- 8.6 GB at fft_size 32768 -- so the
     // factored form needs that intermediate to fit a budget; beyond it the chain runs on the curve itself, as in round 4)
     const size_t dense_bytes = (size_t)plan->anchors() * (size_t)plan->bins() * sizeof(double);
-    const bool factored = !robust && plan->bins() > 4097 && !round4 && dense_bytes <= FIR_FACTOR_DENSE_BUDGET;
+    const bool factored = !robust && plan->bins() > 4097 && !h->fir_round4 && dense_bytes <= FIR_FACTOR_DENSE_BUDGET;
     const bool direct = robust || (!factored && plan->bins() > 8193);
     PlanDev pd;
     {
@@ -725,8 +727,7 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
         int dev_cus = 256;
         HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device));
         auto rounds = [&](int tile) { return (2 * ((pl.bins + tile - 1) / tile) + dev_cus - 1) / dev_cus; };
-        const char* tile32 = std::getenv("MGX_CURVE_TILE32");                    // (A/B: always 32)
-        if (rounds(33) < rounds(32) && !(tile32 && tile32[0] == '1')) {
+        if (rounds(33) < rounds(32)) {
             MGX_TRY(allow_lds(k_match_curve<33>, lds_curve));
             hipLaunchKernelGGL(k_match_curve<33>, dim3((pl.bins + 32) / 33, 2), dim3(1024), lds_curve, h->stream, ct, cr,
                                pl.bins, pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw,
@@ -781,8 +782,8 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     }
     // tap synthesis: the symmetric cosine sum up to 4096 taps (8 us in one launch -- two launches of the split
     // transform cost 10), the split transform from 8192 taps on (13 us against 47 at 16384;
-    // profiles/r03_x_tap_synthesis.txt).  MGX_TAPS_BY_COSINE_SUM=1 forces the sum: the A/B switch of that profile.
-    if (pl.fft >= TAP_TRANSFORM_FROM && !std::getenv("MGX_TAPS_BY_COSINE_SUM")) {
+    // profiles/r03_x_tap_synthesis.txt).
+    if (pl.fft >= TAP_TRANSFORM_FROM) {
         // (65536 taps: sixteen sub-transforms of 2048 points -- the longest one instantiated)
         const int split = pl.fft > 32768 ? 2 * TAP_SPLIT : TAP_SPLIT;
         const int m = pl.fft / 2 / split;
@@ -936,9 +937,7 @@ static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const 
     }
     {
         // 4096 taps (the reference's default fft_size) on 16384-point blocks, three quarters of a block fresh output
-        // (the variable: A/B against N = 2F)
-        const char* no_wide = std::getenv("MGX_NO_CONV_WIDE");
-        if (taps == 4096 && !(no_wide && no_wide[0] == '1')) {
+        if (taps == 4096 && !h->no_conv_wide) {
             constexpr int WIDE = 14;
             MGX_TRY(ensure(h, h->filt, 2 * ((size_t)1 << WIDE) * sizeof(float2)));
             Conv2Args a;
@@ -972,8 +971,7 @@ static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const 
     a.pair_peak = nullptr;
     MGX_TRY(get_twiddles(h, log2b, &a.tw));
     a.run = 0;
-    const char* no_delay = std::getenv("MGX_NO_CONV_DELAY");
-    if (parts == 2 && !(no_delay && no_delay[0] == '1')) {      // (the variable: A/B against the partitioned kernel)
+    if (parts == 2 && !h->no_conv_delay) {
         if (npairs_out) *npairs_out = (n + (long long)nb / 2 - 1) / ((long long)nb / 2);
         return launch_conv_delay<LONG_FIR_LOG2N>(h, a, taps_dev, gain, gain_ptr);
     }
@@ -1001,19 +999,12 @@ static int run_clipped_sumsq(mgx_handle* h, const float* mid, long long piece, i
 }
 
 // look-back words and control block of a limiter launch over n frames (allocated, not initialised)
-// blocks per limiter chunk: the rule of host_params.h, unless MGX_LIMIT_THREADS = 256 / 1024 asks otherwise (measurement
-// aid; read where the parameters are derived so that an A/B inside one process sees it).  Chunks of 512 blocks were
-// built and measured in round 6 for 96 kHz, where the halos eat a quarter of a 256-block chunk: 221 us against 204 (and
-// 306 for 1024 blocks), 84 B of scratch at the 128 registers two workgroups per CU leave -- profiles/r06_b_*; removed.
-static void limiter_threads_from_environment() {
-    const char* e = std::getenv("MGX_LIMIT_THREADS");
-    const int v = e ? std::atoi(e) : 0;
-    limiter_threads_wish() = (v == 256 || v == 1024) ? v : 0;
-}
+// (blocks per limiter chunk: the rule of host_params.h.  Chunks of 512 blocks were built and measured in round 6 for
+// 96 kHz, where the halos eat a quarter of a 256-block chunk: 221 us against 204 (and 306 for 1024 blocks), 84 B of
+// scratch at the 128 registers two workgroups per CU leave -- profiles/r06_b_*; removed.)
 static int limiter_state(mgx_handle* h, long long n, const mgx_config* cfg, unsigned long long** published,
                          long long* words, int** ticket) {
     LimiterParams lp;
-    limiter_threads_from_environment();
     const std::string err = limiter_params(*cfg, lp);
     if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     const long long nchunks = (n + lp.geo.chunk - 1) / lp.geo.chunk;
@@ -1047,16 +1038,14 @@ static int launch_limiter_general(mgx_handle* h, const LimiterArgs& a, const Lim
 // (a persistent grid that fetches a workgroup's next chunk under its current one was built and measured in round 4:
 // 187 against 171 us, profiles/r04_c_persistent_limiter.txt)
 // the 256-block kernel: the instantiation for the configuration's window geometry when there is one (k_limit in
-// mgx_kernels.h; MGX_LIMIT_GENERAL=1: measurement aid, always the general one)
+// mgx_kernels.h)
 static void launch_limiter_256(const LimiterArgs& a, dim3 grid, hipStream_t stream) {
     const size_t lds = LimiterBlock<256>::LDS_BYTES;
-    const char* general = std::getenv("MGX_LIMIT_GENERAL");
-    const bool fixed = !(general && general[0] == '1');
-    if (fixed && a.hw == 44 && a.hb == 43 && a.gr == 26 && a.gl == 6 && a.gw == 3)                 // 44.1 kHz, 1 ms / 1 ms
+    if (a.hw == 44 && a.hb == 43 && a.gr == 26 && a.gl == 6 && a.gw == 3)                 // 44.1 kHz, 1 ms / 1 ms
         hipLaunchKernelGGL((k_limit<256, 4, 44, 43, 26>), grid, dim3(256), lds, stream, a);
-    else if (fixed && a.hw == 48 && a.hb == 47 && a.gr == 28 && a.gl == 6 && a.gw == 3)            // 48 kHz
+    else if (a.hw == 48 && a.hb == 47 && a.gr == 28 && a.gl == 6 && a.gw == 3)            // 48 kHz
         hipLaunchKernelGGL((k_limit<256, 4, 48, 47, 28>), grid, dim3(256), lds, stream, a);
-    else if (fixed && a.hw == 96 && a.hb == 95 && a.gr == 55 && a.gl == 12 && a.gw == 6)           // 96 kHz (BASELINE config #5)
+    else if (a.hw == 96 && a.hb == 95 && a.gr == 55 && a.gl == 12 && a.gw == 6)           // 96 kHz (BASELINE config #5)
         hipLaunchKernelGGL((k_limit<256, 4, 96, 95, 55>), grid, dim3(256), lds, stream, a);
     else
         hipLaunchKernelGGL((k_limit<256, 4>), grid, dim3(256), lds, stream, a);
@@ -1078,7 +1067,6 @@ static int launch_limiter(mgx_handle* h, const LimiterArgs& a, int threads) {
 static int limiter_args(mgx_handle* h, const float* y, long long n, const mgx_config* cfg, const double* gain_dev,
                         const double* post_dev, const int* active_dev, float* out, LimiterArgs& a, int* threads,
                         LimiterParams& lp) {
-    limiter_threads_from_environment();
     const std::string err = limiter_params(*cfg, lp);
     if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     if (n < 8) return fail(MGX_ERR_ARGUMENT, "limiter input too short");
@@ -1120,7 +1108,9 @@ static int run_limiter(mgx_handle* h, const float* y, long long n, const mgx_con
     MGX_TRY(ensure(h, h->lim_published, pub_bytes));
     MGX_TRY(ensure_ctrl(h));
     a.published = (unsigned long long*)h->lim_published.p;
-    const char* force_tickets = std::getenv("MGX_LIMIT_TICKETS");             // measurement aid / tests: "1" = always tickets
+    // "1" = always tickets.  Read here at every launch, not at mgx_create: bench.py and the batch lanes set it at run
+    // time, possibly after the handle exists.
+    const char* force_tickets = std::getenv("MGX_LIMIT_TICKETS");
     a.ticket = (h->limiter_tickets || (force_tickets && force_tickets[0] == '1')) ? (int*)h->lim_ctrl.p : nullptr;
     h->limiter_ran_by_number = h->limiter_ran_by_number || a.ticket == nullptr;     // (since the last error check)
     a.error = h->error_dev;
@@ -1282,6 +1272,12 @@ int mgx_config_default(mgx_config* c) {
     return 0;
 }
 
+// an environment switch: "1" turns it on
+static bool env_flag(const char* name) {
+    const char* e = std::getenv(name);
+    return e && e[0] == '1';
+}
+
 int mgx_create(int device, mgx_handle** out) {
     if (!out) return fail(MGX_ERR_ARGUMENT, "out is null");
     int n = 0;
@@ -1291,6 +1287,11 @@ int mgx_create(int device, mgx_handle** out) {
     HIP_TRY(hipSetDevice(device));
     mgx_handle* h = new mgx_handle();
     h->device = device;
+    // the environment switches, read once here: a host thread's setenv cannot race a running call
+    h->no_conv_wide = env_flag("MGX_NO_CONV_WIDE");
+    h->no_conv_delay = env_flag("MGX_NO_CONV_DELAY");
+    h->fir_round4 = env_flag("MGX_FIR_ROUND4");
+    h->avoid_tail = env_flag("MGX_NO_TAIL");
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&h->ev0));
     HIP_TRY(hipEventCreate(&h->ev1));
@@ -1311,10 +1312,6 @@ int mgx_create(int device, mgx_handle** out) {
         if (!done[device]) {
             int bytes[CODE_KERNELS][CODE_VARIANTS];
             code_sizes_from_library(bytes);
-            if (const char* off = std::getenv("MGX_NO_CODE_WARM"))          // measurement aid (tools/bench_stages.py variants)
-                if (off[0] == '1')
-                    for (auto& row : bytes)
-                        for (int& b : row) b = 0;
             HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mgx::g_code_bytes), bytes, sizeof(bytes)));
             done[device] = true;
         }
@@ -1672,11 +1669,6 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
                        int64_t n_reference, const mgx_config* cfg, const float* fir_given, float* result_dev,
                        float* result_no_limiter_dev, float* result_no_limiter_normalized_dev, mgx_report* report);
 // every launch of one stages.main, queued on the handle's stream (no host round trip)
-static int dev_repeat_default(const char* name, int fallback) {
-    const char* e = std::getenv(name);
-    return e ? std::max(1, std::atoi(e)) : fallback;
-}
-static int dev_repeat(const char* name) { return dev_repeat_default(name, 1); }
 static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     const float* target_dev = c.target;
     const float* reference_dev = c.reference;
@@ -1712,11 +1704,8 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     MGX_TRY(ensure(h, h->y, (size_t)n_target * sizeof(float2)));
     MGX_TRY(ensure(h, h->mid, (size_t)n_target * sizeof(float)));
     long long nblocks = 0;
-    // (MGX_DEV_REPEAT_CONV / MGX_DEV_REPEAT_LIMIT = n: measurement aid, the stage's launches n times in a row -- the
-    // difference between n = 2 and n = 1 is the stage with its code already in the instruction caches)
-    for (int rep = dev_repeat("MGX_DEV_REPEAT_CONV"); rep > 0; --rep)
-        MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)h->taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
-                         &nblocks, (const double*)h->scalars.p));
+    MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)h->taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
+                     &nblocks, (const double*)h->scalars.p));
     // stage 3 (stages.py:138-170): scalar feedback stays on the device; one launch per round, the last
     // round also derives the peak / early-out / normalisation scalars (the state was reset by k_fir_raw)
     CorrectionState* cs = (CorrectionState*)h->cstate.p;
@@ -1727,7 +1716,7 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
         ra.mid = (const float*)h->mid.p;
         ra.piece = tw.piece;
         ra.divisions = tw.divisions;
-        ra.chunks = std::max(1, dev_repeat_default("MGX_ROUND_WGS", 1024) / tw.divisions);     // ~1000 workgroups: each pays one publish + ticket
+        ra.chunks = std::max(1, 1024 / tw.divisions);     // ~1000 workgroups: each pays one publish + ticket
         // (round 0's partial sums, and behind them the peak words of k_correction_tail's workgroups)
         MGX_TRY(ensure(h, h->partial, (size_t)2 * ra.divisions * ra.chunks * sizeof(double)));
         ra.partial = (double*)h->partial.p;
@@ -1737,9 +1726,7 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
         const size_t ctr_bytes = (size_t)(1 + ra.divisions) * sizeof(unsigned);
         // at most ~128 workgroups in k_correction_tail, at most 64 chunks (the lanes of a wave) per workgroup
         const int tail_groups = std::max((ra.chunks + 63) / 64, std::max(1, std::min(ra.chunks, 128 / ra.divisions)));
-        // (MGX_NO_TAIL=1: measurement aid, one launch per correction round for this call)
-        const char* no_tail = std::getenv("MGX_NO_TAIL");
-        const bool use_tail = cfg->rms_correction_steps > 1 && !h->avoid_tail && !(no_tail && no_tail[0] == '1');
+        const bool use_tail = cfg->rms_correction_steps > 1 && !h->avoid_tail;
         const int tail_total = use_tail ? ra.divisions * tail_groups : 0;
         const int tail_rounds = use_tail ? cfg->rms_correction_steps - 1 : 0;
         MGX_TRY(ensure(h, h->tail_gains, ((size_t)tail_rounds + 1 + (size_t)tail_rounds * tail_total) * sizeof(unsigned long long)));
@@ -1832,8 +1819,6 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
         const double* post = &((const TrackStats*)rw.stats.p)->amplitude_c;
         MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, cfg, &cs->gain, post, &cs->limiter_active, result_dev,
                             limiter_preset));
-        for (int rep = dev_repeat("MGX_DEV_REPEAT_LIMIT"); rep > 1; --rep)
-            MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, cfg, &cs->gain, post, &cs->limiter_active, result_dev, false));
     }
     return 0;
 }
@@ -1969,7 +1954,7 @@ int mgx_last_fir(mgx_handle* h, void** taps_dev, int32_t* taps) {
 // ---- RCCL ----------------------------------------------------------------------
 // The ranks of a job are the GPUs of ONE node, the data path between them is xGMI and the bootstrap needs nothing but
 // loop-back -- but telling RCCL so (NCCL_SOCKET_IFNAME=lo, NCCL_IB_DISABLE=1) changes the environment of the HOST
-// process, which is the host's decision and not thread-safe against the getenv calls of a running library: the Python
+// process, which is the host's decision and not thread-safe against a running library's reads of it: the Python
 // front end does it where a job sets itself up (matchering_amd/ranks.py single_node_rccl_defaults), a C / C++ host sets
 // the two variables itself before its first mgx_comm_* call.  Nothing here calls setenv.
 int mgx_comm_unique_id(void* id128) {

@@ -206,7 +206,7 @@ inline void st_f1_in_range(MemView m, unsigned voff, float v) { st_f1<AUX>(m, vo
 // Streaming stores: data this kernel will not read again goes out non-temporal so that it does not
 // evict what is still to be re-read from the L2 (the convolution's input frames, the limiter's).
 MGX_HD void st_stream(float4* p, float4 v) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MGX_HOST_EMU) && !defined(MGX_NO_STREAM_STORES)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MGX_HOST_EMU)
     typedef float v4_t __attribute__((ext_vector_type(4)));
     v4_t t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<v4_t*>(p));
@@ -215,7 +215,7 @@ MGX_HD void st_stream(float4* p, float4 v) {
 #endif
 }
 MGX_HD void st_stream(float2* p, float2 v) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MGX_HOST_EMU) && !defined(MGX_NO_STREAM_STORES)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MGX_HOST_EMU)
     typedef float v2_t __attribute__((ext_vector_type(2)));
     v2_t t = {v.x, v.y};
     __builtin_nontemporal_store(t, reinterpret_cast<v2_t*>(p));

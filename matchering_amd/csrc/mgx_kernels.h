@@ -29,30 +29,24 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // until the last wave arrives; this takes them from ten per block to five.  Other plans get the barrier.
 template <class F>
 __device__ __forceinline__ void pass_sync() {
-#ifdef MGX_PASS_BARRIERS                     // A/B build: a workgroup barrier between all passes, as until round 4
-    lds_barrier();
-#else
     if constexpr (F::WAVE_LOCAL) asm volatile("" ::: "memory");
     else lds_barrier();
-#endif
 }
 
 // The middle passes of a transform, forward and inverse, as the kernels below call them (each followed / preceded by
 // the pass_sync the separate passes had).  A four-pass plan (16384 points) runs its two radix-8 passes as ONE phase
 // with the exchange between them in the wave's lanes (fft2_lanes.h: bit-identical results, one LDS round trip and one
-// wait fewer per direction: k_conv_wide<14> 144.3 -> 139.4 us, k_conv_delay<14> 238.5 -> 232.7, profiles/r06_b_*);
-// -DMGX_SEPARATE_MID_PASSES builds the two-phase form for an A/B.  LANES = false: kernels that hold an accumulator row
+// wait fewer per direction: k_conv_wide<14> 144.3 -> 139.4 us, k_conv_delay<14> 238.5 -> 232.7, profiles/r06_b_*).
+// LANES = false: kernels that hold an accumulator row
 // or a second transform's registers across the middle passes (k_conv<14>, the two- and four-transform analysis) keep
 // the two-phase form -- both butterflies of a thread alive at once is 16 registers they do not have.
 template <class F, bool LANES = true>
 __device__ __forceinline__ void fwd_middle_passes(int tid, float2* lds, const float2* mid_table) {
-#ifndef MGX_SEPARATE_MID_PASSES
     if constexpr (F::P == 4 && LANES) {
         Fft2Lanes<ilog2(F::N)>::fwd_mid_fused(tid, lds, mid_table);
         pass_sync<F>();
         return;
     }
-#endif
     if constexpr (F::P >= 3) {
         F::fwd_mid(tid, lds, mid_table);
         pass_sync<F>();
@@ -64,13 +58,11 @@ __device__ __forceinline__ void fwd_middle_passes(int tid, float2* lds, const fl
 }
 template <class F, bool LANES = true>
 __device__ __forceinline__ void inv_middle_passes(int tid, float2* lds, const float2* mid_table) {
-#ifndef MGX_SEPARATE_MID_PASSES
     if constexpr (F::P == 4 && LANES) {
         pass_sync<F>();
         Fft2Lanes<ilog2(F::N)>::inv_mid_fused(tid, lds, mid_table);
         return;
     }
-#endif
     if constexpr (F::P == 4) {
         pass_sync<F>();
         F::inv_mid2(tid, lds, mid_table);
@@ -458,9 +450,7 @@ __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) v
 // are fetched through the same L2 (until round 6: blocks w, w + G, ... -- neighbours on different XCDs, the shared quarter
 // fetched from HBM twice: FETCH_SIZE 112 MiB x 2 for 169 MB of frames).  Placement affects speed only.
 __device__ __forceinline__ long long conv_wide_block(unsigned w, unsigned round, unsigned grid) {
-#ifndef MGX_CONV_WIDE_STRIDED
     if ((grid & 7u) == 0) return ((long long)round * 8 + (w & 7u)) * (grid >> 3) + (w >> 3);
-#endif
     return (long long)round * grid + w;
 }
 template <int LOG2N>
@@ -497,16 +487,6 @@ __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) v
         DEV_CONV_MARK(1);                   // middle passes
         typename CW::Filters filt;
         CW::fetch_filters(opaque(tid), a, filt);          // needed behind the next barrier
-#ifdef MGX_CONV_WIDE_ROW_IN_LDS                           // A/B build: the whole row through the LDS, as until round 6
-        CW::phase_row(opaque(tid), lds);
-        lds_barrier();
-        DEV_CONV_MARK(2);                   // row forward, barrier
-        CW::phase_multiply(opaque(tid), filt, lds);
-        lds_barrier();                    // the partner has written this row's upper half
-        __builtin_amdgcn_sched_barrier(0);
-        DEV_CONV_MARK(3);                   // multiply, barrier
-        CW::phase_row_back(opaque(tid), lds);
-#else
         typename CW::Kept kept;                           // the own half of the row stays in registers (conv_wide_kernel.h)
         CW::phase_row_keep(opaque(tid), kept, lds);
         lds_barrier();
@@ -516,7 +496,6 @@ __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) v
         __builtin_amdgcn_sched_barrier(0);
         DEV_CONV_MARK(3);                   // multiply, barrier
         CW::phase_row_back_keep(opaque(tid), kept, lds);
-#endif
         inv_middle_passes<F>(opaque(tid), lds, mid_table);
         // the next block's window: its latency under the last inverse pass and the stores -- the barriers from here
         // to the top of the loop order LDS traffic only (a __syncthreads() would wait for these loads)
@@ -581,14 +560,12 @@ constexpr size_t analysis_lds_bytes() {
 }
 
 // waves per SIMD the LDS footprint admits (4 SIMDs per CU): the register budget follows from it
-#ifndef MGX_ANALYZE_MAX_WGS
-#define MGX_ANALYZE_MAX_WGS 8          // experiments: cap the workgroups per CU (more registers each)
-#endif
+constexpr int ANALYZE_MAX_WGS = 8;      // workgroups per CU at most (host: analysis_workgroups_per_cu)
 template <int LOG2N>
 constexpr int analysis_waves_per_simd() {
     constexpr int by_lds = (int)((size_t)160 * 1024 / analysis_lds_bytes<LOG2N>());
-    constexpr int wgs = by_lds < MGX_ANALYZE_MAX_WGS ? by_lds : MGX_ANALYZE_MAX_WGS;
-    constexpr int w = (wgs > 8 ? 8 : wgs) * (Fft2<LOG2N>::T / 64) / 4;
+    constexpr int wgs = by_lds < ANALYZE_MAX_WGS ? by_lds : ANALYZE_MAX_WGS;
+    constexpr int w = wgs * (Fft2<LOG2N>::T / 64) / 4;
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
 
@@ -616,13 +593,7 @@ __global__ __launch_bounds__(Fft2<LOG2N>::T, analysis_waves_per_simd<LOG2N>()) v
     __syncthreads();
     int s0, s1;
     AB::chunk_segments(a, ch, s0, s1);
-#ifdef MGX_ANALYZE_NOT_AHEAD                 // A/B build: every segment's frames asked for at its top, as until round 6
-    constexpr bool AHEAD = false;
-#elif defined(MGX_ANALYZE_AHEAD_ALL)        // experiment: the smaller transforms too
-    constexpr bool AHEAD = LOG2N >= 11;
-#else
     constexpr bool AHEAD = LOG2N == 14;
-#endif
     typename AB::Raw raw;
     if (AHEAD) AB::fetch(tid, (long long)d * a.piece + (long long)s0 * F::N, a, raw);
     for (int s = s0; s < s1; ++s) {
@@ -1996,63 +1967,46 @@ __global__ __launch_bounds__(256) void k_correction_round(RoundArgs a) {
             // the float64 sums -- and the band samples are compacted per THREAD: each thread counts its
             // own, one prefix sum over the wave places them, no ballot and no scalar chain per sample.
             // (A frame past the end loads as 0: clips to 0, counts as never clipped, adds nothing.)
-            // MGX_ROUND0_GROUPS x four 16-byte loads per thread in flight, each group of sixteen samples then summed and
-            // compacted in order (bit-identical whatever the number).  One group is the product: two and three were
-            // measured in round 6 -- the whole stage 52.1 -> 54.2 / 54.3 us -- as were more, shorter workgroups (51.5 ->
-            // 56.1 at twice as many): this kernel is not short of loads in flight (profiles/r06_b_*, r06_g_*).
-#ifndef MGX_ROUND0_GROUPS
-#define MGX_ROUND0_GROUPS 1
-#endif
-            constexpr int GROUPS = MGX_ROUND0_GROUPS;
-            for (long long s0 = head; s0 < body_end; s0 += GROUPS * 4 * 1024) {
-                float xs[GROUPS][16];
+            // Four 16-byte loads per thread in flight, the sixteen samples then summed and compacted in order.  Two and
+            // three such groups in flight were measured in round 6 -- the whole stage 52.1 -> 54.2 / 54.3 us -- as were
+            // more, shorter workgroups (51.5 -> 56.1 at twice as many): this kernel is not short of loads in flight
+            // (profiles/r06_b_*, r06_g_*).
+            for (long long s0 = head; s0 < body_end; s0 += 4 * 1024) {
+                float x[16];
 #pragma unroll
-                for (int gq = 0; gq < GROUPS; ++gq) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const long long i = s0 + (gq * 4 + u) * 1024 + 4ll * threadIdx.x;
-                        const float4 q = i < body_end ? *reinterpret_cast<const float4*>(a.mid + i) : make_float4(0.f, 0.f, 0.f, 0.f);
-                        xs[gq][4 * u] = q.x; xs[gq][4 * u + 1] = q.y; xs[gq][4 * u + 2] = q.z; xs[gq][4 * u + 3] = q.w;
-                    }
+                for (int u = 0; u < 4; ++u) {
+                    const long long i = s0 + u * 1024 + 4ll * threadIdx.x;
+                    const float4 q = i < body_end ? *reinterpret_cast<const float4*>(a.mid + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    x[4 * u] = q.x; x[4 * u + 1] = q.y; x[4 * u + 2] = q.z; x[4 * u + 3] = q.w;
                 }
+                float sq = 0.f, lo = 0.f;
+                int mine = 0;
+                unsigned bits = 0;
 #pragma unroll
-                for (int gq = 0; gq < GROUPS; ++gq) {
-                    const float (&x)[16] = xs[gq];
-                    float sq = 0.f, lo = 0.f;
-                    int mine = 0;
-                    unsigned bits = 0;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const float c = __builtin_amdgcn_fmed3f(x[i], -1.0f, 1.0f);
-                        sq = fmaf(c, c, sq);
-                        const float m = fabsf(x[i]);
-                        const bool never = m <= t_never, always = m >= t_always;
-                        lo = fmaf(never ? x[i] : 0.f, x[i], lo);
-                        clipped_mine += always ? 1 : 0;
-                        const bool in_band = !never && !always;
-                        mine += in_band ? 1 : 0;
-                        bits |= (in_band ? 1u : 0u) << i;
-                    }
-                    acc += (double)sq;
-                    low += (double)lo;
-#ifdef MGX_DEV_ROUND0_SUMS_ONLY         // development builds only: what round 0 costs without its band lists (results are wrong)
-                    const int through = mine;
-                    int slot = filled;
-                    if (false) {
-#else
-                    const int through = wave_inclusive_sum(mine);
-                    int slot = filled + through - mine;
-                    if (bits) {
-#endif
-#pragma unroll
-                        for (int i = 0; i < 16; ++i)
-                            if (bits & (1u << i)) {
-                                if (slot < bc.wave_cap) wave_band[slot] = x[i];
-                                ++slot;
-                            }
-                    }
-                    filled += __builtin_amdgcn_readlane(through, 63);
+                for (int i = 0; i < 16; ++i) {
+                    const float c = __builtin_amdgcn_fmed3f(x[i], -1.0f, 1.0f);
+                    sq = fmaf(c, c, sq);
+                    const float m = fabsf(x[i]);
+                    const bool never = m <= t_never, always = m >= t_always;
+                    lo = fmaf(never ? x[i] : 0.f, x[i], lo);
+                    clipped_mine += always ? 1 : 0;
+                    const bool in_band = !never && !always;
+                    mine += in_band ? 1 : 0;
+                    bits |= (in_band ? 1u : 0u) << i;
                 }
+                acc += (double)sq;
+                low += (double)lo;
+                const int through = wave_inclusive_sum(mine);
+                int slot = filled + through - mine;
+                if (bits) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i)
+                        if (bits & (1u << i)) {
+                            if (slot < bc.wave_cap) wave_band[slot] = x[i];
+                            ++slot;
+                        }
+                }
+                filled += __builtin_amdgcn_readlane(through, 63);
             }
         } else
         for (long long s0 = head; s0 < body_end; s0 += 4 * 1024) {

@@ -245,8 +245,9 @@ extern "C" int emu_convolve_delay(const float* x, long long n, const double* fir
 }
 
 // ---------------------------------------------------------------------------
-// F taps on N = 4F blocks (conv_wide_kernel.h): the phase sequence of k_conv_wide in mgx_kernels.h
-template <int LOG2N>
+// F taps on N = 4F blocks (conv_wide_kernel.h): the phase sequence of k_conv_wide in mgx_kernels.h.  KEEP: the *_keep
+// phases the kernel runs; otherwise the whole row through the LDS, their reference
+template <int LOG2N, bool KEEP>
 static int conv_wide_impl(const float* x, long long n, const double* fir_mid, const double* fir_side, int taps,
                           double gain, float* y, float* ymid, float* block_peak) {
     using CW = ConvWide<LOG2N>;
@@ -284,12 +285,20 @@ static int conv_wide_impl(const float* x, long long n, const double* fir_mid, co
             CW::phase_pass0(tid, ps[tid], fr, lds.data());
         }
         std::vector<typename CW::Filters> filt(F::T);
+        std::vector<typename CW::Kept> kept(F::T);           // the own half of each thread's row, in its registers
         local_phases<F>(mid_phases<F>(false, lds.data(), mid_table.data()) + std::vector<Phase>{[&](int tid) {
                             CW::fetch_filters(tid, a, filt[tid]);
-                            CW::phase_row(tid, lds.data());
+                            if (KEEP) CW::phase_row_keep(tid, kept[tid], lds.data());
+                            else CW::phase_row(tid, lds.data());
                         }});
-        FOR_THREADS(F::T) CW::phase_multiply(tid, filt[tid], lds.data());   // (mirror rows: a barrier either side)
-        local_phases<F>(std::vector<Phase>{[&](int tid) { CW::phase_row_back(tid, lds.data()); }} +
+        FOR_THREADS(F::T) {                                 // (mirror rows: a barrier either side)
+            if (KEEP) CW::phase_multiply_keep(tid, filt[tid], kept[tid], lds.data());
+            else CW::phase_multiply(tid, filt[tid], lds.data());
+        }
+        local_phases<F>(std::vector<Phase>{[&](int tid) {
+                            if (KEEP) CW::phase_row_back_keep(tid, kept[tid], lds.data());
+                            else CW::phase_row_back(tid, lds.data());
+                        }} +
                         mid_phases<F>(true, lds.data(), mid_table.data()));
         float pk = 0.f;
         FOR_THREADS(F::T) pk = std::fmax(pk, CW::phase_store(tid, b, a, ps[tid], lds.data()));
@@ -297,14 +306,23 @@ static int conv_wide_impl(const float* x, long long n, const double* fir_mid, co
     }
     return 0;
 }
-extern "C" int emu_convolve_wide(const float* x, long long n, const double* fir_mid, const double* fir_side, int taps,
-                                 double gain, float* y, float* ymid, float* block_peak) {
+template <bool KEEP>
+static int conv_wide(const float* x, long long n, const double* fir_mid, const double* fir_side, int taps, double gain,
+                     float* y, float* ymid, float* block_peak) {
     switch (ilog2_exact(taps)) {
-#define CASE(L) case L - 2: return conv_wide_impl<L>(x, n, fir_mid, fir_side, taps, gain, y, ymid, block_peak);
+#define CASE(L) case L - 2: return conv_wide_impl<L, KEEP>(x, n, fir_mid, fir_side, taps, gain, y, ymid, block_peak);
         CASE(11) CASE(12) CASE(13) CASE(14)
 #undef CASE
         default: return -4;
     }
+}
+extern "C" int emu_convolve_wide(const float* x, long long n, const double* fir_mid, const double* fir_side, int taps,
+                                 double gain, float* y, float* ymid, float* block_peak) {
+    return conv_wide<true>(x, n, fir_mid, fir_side, taps, gain, y, ymid, block_peak);
+}
+extern "C" int emu_convolve_wide_row_in_lds(const float* x, long long n, const double* fir_mid, const double* fir_side,
+                                            int taps, double gain, float* y, float* ymid, float* block_peak) {
+    return conv_wide<false>(x, n, fir_mid, fir_side, taps, gain, y, ymid, block_peak);
 }
 
 // ---------------------------------------------------------------------------

@@ -170,3 +170,24 @@ def test_the_hot_kernels_do_not_spill():
         hit = [limit for fragment, limit in ceilings.items() if fragment in name]
         assert hit, f"{name} spills {entry['scratch']} B per lane and has no ceiling in this test"
         assert entry["scratch"] <= hit[0], (name, entry["scratch"], hit[0])
+
+
+def test_the_library_source_holds_no_retired_switches():
+    """(no GPU, no compiler) The library's source is the product: an environment switch selects a path a test compares
+    the product against (read at mgx_create) or is MGX_LIMIT_TICKETS, and a preprocessor switch builds the CPU emulation,
+    a ROCm without the profiler SDK, a fault-injection test build or an instrumentation build for tools/.  A variant that
+    was measured and lost lives in git history (docs/HISTORY.md), not behind a switch."""
+    csrc = os.path.join(ROOT, "matchering_amd", "csrc")
+    code = ""
+    for name in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, name)) as fh:
+            code += re.sub(r"//[^\n]*", "", fh.read()) + "\n"
+    read = set(re.findall(r'\b(?:getenv|env_flag)\("(MGX_\w+)"\)', code))
+    assert read == {"MGX_NO_CONV_DELAY", "MGX_NO_CONV_WIDE", "MGX_FIR_ROUND4", "MGX_NO_TAIL", "MGX_LIMIT_TICKETS"}
+    assert len(re.findall(r'\bgetenv\((?!")', code)) == 1          # env_flag's own read; it is called with names only
+    assert re.findall(r'\benv_flag\((?!")', code) == ["env_flag("]
+    keep = {"MGX_HOST_EMU", "MGX_NO_ROCTX", "MGX_DEV_CONV_PHASES", "MGX_DEV_LIMITER_PHASES", "MGX_TAIL_TRACE"}
+    conditions = re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b([^\n]*)", code, flags=re.M)
+    switches = {m for c in conditions for m in re.findall(r"\bMGX_\w+", c)}
+    assert switches, "no preprocessor conditions found"
+    assert {m for m in switches if m not in keep and not m.startswith("MGX_TEST_")} == set()

@@ -136,6 +136,12 @@ def test_wide_block_convolution_phases(emu, taps, n):
     assert rms_error(ymid, want_mid) <= 1e-6
     for b in range(nblocks):
         assert abs(peaks[b] - np.abs(y[b * hop:(b + 1) * hop]).max()) <= 1e-6
+    # the kernel keeps its own half of a row in registers; the whole row through the LDS gives the same bits
+    y2, ymid2, peaks2 = np.zeros_like(y), np.zeros_like(ymid), np.zeros_like(peaks)
+    rc = emu.emu_convolve_wide_row_in_lds(_fp(x), ctypes.c_longlong(n), _dp(hm), _dp(hs), ctypes.c_int(taps),
+                                          ctypes.c_double(1.3), _fp(y2), _fp(ymid2), _fp(peaks2))
+    assert rc == 0
+    assert np.array_equal(y, y2) and np.array_equal(ymid, ymid2) and np.array_equal(peaks, peaks2)
 
 
 def test_wide_and_delay_line_kernels_over_random_lengths(emu):

@@ -8,6 +8,7 @@ bounds where a stage is checked on its own.
 """
 
 import os
+from contextlib import closing
 
 import numpy as np
 import pytest
@@ -183,6 +184,7 @@ def test_two_partition_filter_as_a_delay_line(n, monkeypatch):
     product carried from block to block of a workgroup's run (k_conv_delay).  Track lengths from one frame to runs of
     six blocks per workgroup, against fftconvolve and against the partitioned kernel it replaces."""
     from matchering_amd import kernels
+    from matchering_amd.device import Device
 
     taps = 16384
     rng = np.random.RandomState(n % 100000)
@@ -194,8 +196,9 @@ def test_two_partition_filter_as_a_delay_line(n, monkeypatch):
     assert rms_error(y, want) <= 1e-6
     assert rms_error(ymid, want_mid) <= 1e-6
     assert abs(peak - np.abs(y).max()) <= 1e-6
-    monkeypatch.setenv("MGX_NO_CONV_DELAY", "1")
-    y2, ymid2, peak2 = kernels.convolve(x, hm, hs, gain=0.9)
+    monkeypatch.setenv("MGX_NO_CONV_DELAY", "1")            # (read when a handle is created)
+    with closing(Device(0)) as dev:
+        y2, ymid2, peak2 = kernels.convolve(x, hm, hs, gain=0.9, device=dev)
     assert np.abs(y - y2).max() <= 5e-6 and np.abs(ymid - ymid2).max() <= 5e-6 and abs(peak - peak2) <= 5e-6
 
 
@@ -204,6 +207,7 @@ def test_default_filter_on_wide_blocks(n, monkeypatch):
     """4096 taps (the reference's default fft_size) on 16384-point blocks, three quarters of a block fresh output
     (k_conv_wide): from one frame to more blocks than workgroups, against fftconvolve and against the N = 2F kernel."""
     from matchering_amd import kernels
+    from matchering_amd.device import Device
 
     taps = 4096
     rng = np.random.RandomState(n % 100000)
@@ -215,8 +219,9 @@ def test_default_filter_on_wide_blocks(n, monkeypatch):
     assert rms_error(y, want) <= 1e-6
     assert rms_error(ymid, want_mid) <= 1e-6
     assert abs(peak - np.abs(y).max()) <= 1e-6
-    monkeypatch.setenv("MGX_NO_CONV_WIDE", "1")
-    y2, ymid2, peak2 = kernels.convolve(x, hm, hs, gain=1.1)
+    monkeypatch.setenv("MGX_NO_CONV_WIDE", "1")             # (read when a handle is created)
+    with closing(Device(0)) as dev:
+        y2, ymid2, peak2 = kernels.convolve(x, hm, hs, gain=1.1, device=dev)
     assert np.abs(y - y2).max() <= 5e-6 and np.abs(ymid - ymid2).max() <= 5e-6 and abs(peak - peak2) <= 5e-6
 
 
@@ -238,14 +243,15 @@ def test_master_long_fir_96k():
         assert np.abs(mine - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max())
 
 
-def _master_with_taps(t, r, cfg):
-    """stages.main's three outputs through the device API, plus the FIR pair the call designed (mgx_last_fir)."""
+def _master_with_taps(t, r, cfg, device=None):
+    """stages.main's three outputs through the device API, plus the FIR pair the call designed (mgx_last_fir), on
+    ``device`` (default: the process-wide one)."""
     import ctypes
 
     from matchering_amd._native import check, library
     from matchering_amd.device import default_device
 
-    dev = default_device()
+    dev = device or default_device()
     with dev.lock:
         td, rd = dev.upload(t), dev.upload(r)
         outs = [dev.alloc(t.shape[0] * 8) for _ in range(3)]
@@ -297,14 +303,16 @@ def test_factored_fir_operator_equals_the_round_4_paths(fft, monkeypatch):
     few MB) against what it replaces -- the dense 537 MB operator at 16384, the chain run on the curve itself at
     32768 (MGX_FIR_ROUND4=1).  The same linear map summed in another order: taps equal to float32 rounding."""
     import matchering_amd as mg
+    from matchering_amd.device import Device
     from matchering_amd.synth import make_pair
 
     sr = 96000
     t, r = make_pair(3.0, sr, pair=9, reference_seconds=2.6)
     cfg = mg.Config(internal_sample_rate=sr, fft_size=fft, max_piece_size=1.1)
     res, fir = _master_with_taps(t, r, cfg)
-    monkeypatch.setenv("MGX_FIR_ROUND4", "1")
-    res4, fir4 = _master_with_taps(t, r, cfg)
+    monkeypatch.setenv("MGX_FIR_ROUND4", "1")               # (read when a handle is created)
+    with closing(Device(0)) as dev:
+        res4, fir4 = _master_with_taps(t, r, cfg, device=dev)
     assert np.abs(fir - fir4).max() <= 2e-7 * np.abs(fir4).max()
     for a, b in zip(res, res4):
         assert np.abs(a - b).max() <= 2e-6
