@@ -148,9 +148,17 @@ static void code_sizes_from_library(int (&bytes)[CODE_KERNELS][CODE_VARIANTS]) {
 // ---------------------------------------------------------------------------
 // handle
 // ---------------------------------------------------------------------------
+// a device allocation that frees itself (the handle's buffers, and the temporaries of the FIR operator builds on every
+// way out, the failing ones included)
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
 };
 
 struct TrackWork {              // per-track analysis workspace + results (device)
@@ -200,6 +208,7 @@ static LimiterChain g_limiter_chain[MAX_DEVICES];
 
 struct mgx_handle {
     int device = 0;
+    int cus = 0;                            // compute units of the device (read at mgx_create)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool stage_timing = false;                                    // mgx_stage_timing
@@ -233,6 +242,7 @@ struct mgx_handle {
         const float* fir_given = nullptr;
         int64_t n_target = 0, n_reference = 0;
         mgx_config cfg;
+        LimiterParams lp;                   // derived from cfg when out[0] (the limited result) is wanted
         float* out[3] = {nullptr, nullptr, nullptr};
     } last_call;
     bool avoid_tail = false;                // sticky after such a report: rounds 1..K-1 as one launch each (MGX_NO_TAIL=1: always)
@@ -389,15 +399,16 @@ static int analysis_workgroups_per_cu(int log2f) {
         case 16: lds = analysis_lds_bytes<14>(); threads = Fft2<14>::T; break;       // four
         default: return 1;
     }
-    const int by_lds = (int)((size_t)160 * 1024 / lds), by_waves = 2048 / threads;
-    return std::max(1, std::min(ANALYZE_MAX_WGS, std::min(by_lds, by_waves)));
+    return std::min(ANALYZE_MAX_WGS, workgroups_per_cu(threads, lds));
 }
 
+// `kernel` runs transforms of 2^LOG2N points: k_analyze<LOG2N>, or k_analyze_double / k_analyze_quad on 16384 points
 template <int LOG2N>
-static int launch_analysis(mgx_handle* h, const AnalysisArgs& a0, const AnalysisArgs& a1, int nwg0, int nwg) {
+static int launch_analysis(mgx_handle* h, void (*kernel)(AnalysisArgs, AnalysisArgs, int), const AnalysisArgs& a0,
+                           const AnalysisArgs& a1, int nwg0, int nwg) {
     const size_t lds = analysis_lds_bytes<LOG2N>();
-    MGX_TRY(allow_lds(k_analyze<LOG2N>, lds));
-    hipLaunchKernelGGL(k_analyze<LOG2N>, dim3(nwg), dim3(Fft2<LOG2N>::T), lds, h->stream, a0, a1, nwg0);
+    MGX_TRY(allow_lds(kernel, lds));
+    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(Fft2<LOG2N>::T), lds, h->stream, a0, a1, nwg0);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -421,8 +432,6 @@ static int plan_analysis(mgx_handle* h, long long n, const mgx_config* cfg, int 
 // workgroup.  Pick the segments per workgroup that minimise it over ALL tracks of the launch (ties:
 // more workgroups); a second dispatch wave of a few stragglers would double the kernel's duration.
 static int choose_chunks(mgx_handle* h, const mgx_config* cfg, TrackWork* const* tracks, int count) {
-    int dev_cus = 256;
-    HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device));
     const int per_cu = analysis_workgroups_per_cu(ilog2_exact(cfg->fft_size));
     int longest = 1;
     for (int t = 0; t < count; ++t) longest = std::max(longest, tracks[t]->segs_per_piece);
@@ -432,7 +441,7 @@ static int choose_chunks(mgx_handle* h, const mgx_config* cfg, TrackWork* const*
         long long wgs = 0;
         for (int t = 0; t < count; ++t)
             wgs += (long long)tracks[t]->divisions * ((tracks[t]->segs_per_piece + s - 1) / s);
-        const long long deep = (wgs + dev_cus - 1) / dev_cus;
+        const long long deep = (wgs + h->cus - 1) / h->cus;
         if (deep > per_cu) continue;
         const long long cost = deep * s;
         if (best_cost < 0 || cost < best_cost) {
@@ -493,23 +502,11 @@ static int run_analysis(mgx_handle* h, const mgx_config* cfg, const float* x0, l
 #define SMALL(L) case L: hipLaunchKernelGGL(k_analyze_small<L>, dim3(nwg), dim3(256), 0, h->stream, a0, a1, w0.nwg); HIP_TRY(hipGetLastError()); break;
         SMALL(3) SMALL(4) SMALL(5)
 #undef SMALL
-#define CASE(L) case L: MGX_TRY(launch_analysis<L>(h, a0, a1, w0.nwg, nwg)); break;
+#define CASE(L) case L: MGX_TRY(launch_analysis<L>(h, k_analyze<L>, a0, a1, w0.nwg, nwg)); break;
         CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14)
 #undef CASE
-        case 15: {
-            const size_t lds = analysis_lds_bytes<14>();
-            MGX_TRY(allow_lds(k_analyze_double<14>, lds));
-            hipLaunchKernelGGL(k_analyze_double<14>, dim3(nwg), dim3(Fft2<14>::T), lds, h->stream, a0, a1, w0.nwg);
-            HIP_TRY(hipGetLastError());
-            break;
-        }
-        case 16: {
-            const size_t lds = analysis_lds_bytes<14>();
-            MGX_TRY(allow_lds(k_analyze_quad<14>, lds));
-            hipLaunchKernelGGL(k_analyze_quad<14>, dim3(nwg), dim3(Fft2<14>::T), lds, h->stream, a0, a1, w0.nwg);
-            HIP_TRY(hipGetLastError());
-            break;
-        }
+        case 15: MGX_TRY(launch_analysis<14>(h, k_analyze_double<14>, a0, a1, w0.nwg, nwg)); break;
+        case 16: MGX_TRY(launch_analysis<14>(h, k_analyze_quad<14>, a0, a1, w0.nwg, nwg)); break;
         default: return fail(MGX_ERR_UNSUPPORTED, "fft_size not supported by the analysis kernel");
     }
     return 0;
@@ -542,7 +539,7 @@ static int run_levels(mgx_handle* h, const mgx_config* cfg, TrackWork* first, Tr
     const int tracks = second ? 2 : 1, half = cfg->fft_size / 2;
     const int max_div = std::max(first->divisions, second ? second->divisions : 0);
     const size_t lds = (size_t)(64 + max_div) * sizeof(double);
-    if (lds > 150 * 1024) return fail(MGX_ERR_UNSUPPORTED, "too many analysis pieces");
+    if (lds > LDS_PER_WORKGROUP_MAX) return fail(MGX_ERR_UNSUPPORTED, "too many analysis pieces");
     MGX_TRY(allow_lds(k_levels, lds));
     for (TrackWork* w : {first, second})
         if (w) MGX_TRY(ensure(h, w->part, (size_t)SPEC_SLICES * 2 * (half + 1) * sizeof(double)));
@@ -585,19 +582,11 @@ static int build_fir_operator(mgx_handle* h, const FirPlanView& pl, double** out
     return 0;
 }
 
-// device temporaries of the operator builds: freed on every way out, the failing ones included
-struct DevTemp {
-    void* p = nullptr;
-    ~DevTemp() { if (p) hipFree(p); }
-    DevTemp() = default;
-    DevTemp(const DevTemp&) = delete;
-    DevTemp& operator=(const DevTemp&) = delete;
-};
 constexpr size_t FIR_FACTOR_DENSE_BUDGET = (size_t)1 << 30;      // 1 GiB for a factor's dense intermediate
 
 // A dense [rows][cols] matrix -> its rows' windows (k_fir_band), packed.  The dense matrix stays the caller's.
 static int pack_fir_factor(mgx_handle* h, double* dense, int rows, int cols, PlanDev::Factor& f) {
-    DevTemp band_tmp;
+    DevBuf band_tmp;
     HIP_TRY(hipMalloc(&band_tmp.p, (size_t)rows * sizeof(int2)));
     int2* band_dev = (int2*)band_tmp.p;
     hipLaunchKernelGGL(k_fir_band, dim3(rows), dim3(256), 0, h->stream, (const double*)dense, cols, band_dev);
@@ -628,7 +617,7 @@ static int pack_fir_factor(mgx_handle* h, double* dense, int rows, int cols, Pla
 static int build_fir_factors(mgx_handle* h, const FirPlanView& pl, PlanDev& pd) {
     const size_t per = (size_t)3 * pl.bins + (size_t)3 * pl.nlog + pl.lw.anchors;
     const int anchors = pl.lw.anchors, batch = 256;
-    DevTemp scratch_tmp, dense_tmp;
+    DevBuf scratch_tmp, dense_tmp;
     HIP_TRY(hipMalloc(&scratch_tmp.p, (size_t)batch * per * sizeof(double)));
     double* scratch = (double*)scratch_tmp.p;
     const size_t lds_scan = (size_t)FirDesign::Scan::SCRATCH * sizeof(Affine);
@@ -720,24 +709,17 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     // tables fit a workgroup's LDS (always, short of thousands of pieces), three otherwise
     const int max_div = std::max(tw.divisions, rw.divisions);
     const size_t lds_curve = match_curve_lds_bytes(max_div, tw.nwg + rw.nwg);
-    if (lds_curve <= (size_t)150 * 1024) {
+    if (lds_curve <= LDS_PER_WORKGROUP_MAX) {
         CurveTrack ct{levels_args(tw), (const float*)tw.wg_spec.p, tw.nwg, tw.segs_per_piece};
         CurveTrack cr{levels_args(rw), (const float*)rw.wg_spec.p, rw.nwg, rw.segs_per_piece};
         // tiles of 33 bins where they save a round of workgroups (one workgroup of 1024 threads per CU)
-        int dev_cus = 256;
-        HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device));
-        auto rounds = [&](int tile) { return (2 * ((pl.bins + tile - 1) / tile) + dev_cus - 1) / dev_cus; };
-        if (rounds(33) < rounds(32)) {
-            MGX_TRY(allow_lds(k_match_curve<33>, lds_curve));
-            hipLaunchKernelGGL(k_match_curve<33>, dim3((pl.bins + 32) / 33, 2), dim3(1024), lds_curve, h->stream, ct, cr,
-                               pl.bins, pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw,
-                               (double*)h->scalars.p, (CorrectionState*)h->cstate.p, h->error_dev);
-        } else {
-            MGX_TRY(allow_lds(k_match_curve<32>, lds_curve));
-            hipLaunchKernelGGL(k_match_curve<32>, dim3((pl.bins + 31) / 32, 2), dim3(1024), lds_curve, h->stream, ct, cr,
-                               pl.bins, pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw,
-                               (double*)h->scalars.p, (CorrectionState*)h->cstate.p, h->error_dev);
-        }
+        auto rounds = [&](int tile) { return (2 * ((pl.bins + tile - 1) / tile) + h->cus - 1) / h->cus; };
+        const int tile = rounds(33) < rounds(32) ? 33 : 32;
+        const auto curve = tile == 33 ? k_match_curve<33> : k_match_curve<32>;
+        MGX_TRY(allow_lds(curve, lds_curve));
+        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->stream, ct, cr, pl.bins,
+                           pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)h->scalars.p,
+                           (CorrectionState*)h->cstate.p, h->error_dev);
     } else {
         TrackWork& t = const_cast<TrackWork&>(tw);
         TrackWork& r = const_cast<TrackWork&>(rw);
@@ -813,102 +795,77 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     return 0;
 }
 
-template <int LOG2N, bool MULTI>
-static int launch_conv(mgx_handle* h, Conv2Args a, const float* taps_dev, double gain, const double* gain_ptr) {
-    using F = Fft2<LOG2N>;
-    const size_t lds = conv_lds_bytes<LOG2N>();
-    MGX_TRY((allow_lds(k_conv_prep<LOG2N>, lds)));
-    MGX_TRY((allow_lds(k_conv<LOG2N, MULTI>, lds)));
-    {
-        StageScope scope(h, MGX_STAGE_FILTER_SPECTRA);
-        hipLaunchKernelGGL((k_conv_prep<LOG2N>), dim3(2 * a.parts), dim3(F::T), lds, h->stream, taps_dev,
-                           a.tw, (float2*)h->filt.p, a.parts, gain_ptr, gain);
-    }
-    HIP_TRY(hipGetLastError());
-    MGX_TRY(ensure(h, h->block_peak, (size_t)a.npairs * sizeof(float)));
-    a.pair_peak = (float*)h->block_peak.p;
-    if (!h->conv_queue.p) {                  // zero once: every launch leaves the counters at zero
-        MGX_TRY(ensure(h, h->conv_queue, 64));
-        HIP_TRY(hipMemsetAsync(h->conv_queue.p, 0, 64, h->stream));
-    }
-    a.queue = (unsigned*)h->conv_queue.p;
-    // persistent grid: as many workgroups as fit the chip at once (LDS-limited), a multiple of 8
-    int dev_cus = 256;
-    HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const int per_cu = std::max(1, std::min(2048 / F::T, (int)((size_t)160 * 1024 / lds)));
-    const long long cap = (long long)dev_cus * per_cu;
-    const unsigned grid = (unsigned)(((std::min<long long>(a.npairs, cap) + 7) / 8) * 8);
-    {
-        StageScope scope(h, MGX_STAGE_CONVOLVE);
-        hipLaunchKernelGGL((k_conv<LOG2N, MULTI>), dim3(grid), dim3(F::T), lds, h->stream, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+// The FFT convolution (run_conv) comes in three forms.  They share one launch path: the filter spectra under
+// MGX_STAGE_FILTER_SPECTRA, a peak per block in h->block_peak, a grid sized by the workgroups the chip holds at once,
+// and the main kernel under MGX_STAGE_CONVOLVE.  They differ in their filter-spectra kernel, block hop and grid:
+//   CONV_QUEUE: k_conv<LOG2N, MULTI> on blocks of N frames; a persistent grid, a multiple of 8, that draws its blocks
+//               from the queue counters
+//   CONV_DELAY: k_conv_delay<LOG2N>, taps = N in two partitions (config #5: 16384 taps on N = 16384 blocks), the
+//               frequency-domain delay line of conv_delay_kernel.h; blocks of N/2 frames, a run of consecutive blocks
+//               per workgroup (every run costs one extra forward transform, so runs are as long as the chip allows)
+//   CONV_WIDE:  k_conv_wide<LOG2N>, F taps on N = 4F (conv_wide_kernel.h; F = 4096 on N = 16384); blocks of 3N/4
+//               frames, one per workgroup, dealt round-robin
+enum ConvForm { CONV_QUEUE, CONV_DELAY, CONV_WIDE };
 
-// taps = N in two partitions (config #5: 16384 taps on N = 16384 blocks): the frequency-domain delay line of
-// conv_delay_kernel.h, a run of consecutive blocks per workgroup (one workgroup per CU: every run costs one extra
-// forward transform, so runs are as long as the chip allows).  a.npairs counts blocks on return.
-template <int LOG2N>
-static int launch_conv_delay(mgx_handle* h, Conv2Args a, const float* taps_dev, double gain, const double* gain_ptr) {
+// *blocks: the number of blocks, one peak each in h->block_peak
+template <int LOG2N, ConvForm FORM, bool MULTI = false>
+static int launch_conv(mgx_handle* h, Conv2Args a, const float* taps_dev, double gain, const double* gain_ptr,
+                       long long* blocks) {
     using F = Fft2<LOG2N>;
     const size_t lds = conv_lds_bytes<LOG2N>();
-    MGX_TRY((allow_lds(k_conv_prep<LOG2N>, lds)));
-    MGX_TRY((allow_lds(k_conv_delay<LOG2N>, lds)));
+    void (*kernel)(Conv2Args);
+    long long hop;                                              // input frames from one block to the next
+    if constexpr (FORM == CONV_QUEUE) {
+        kernel = k_conv<LOG2N, MULTI>;
+        hop = F::N;
+    } else if constexpr (FORM == CONV_DELAY) {
+        kernel = k_conv_delay<LOG2N>;
+        hop = ConvDelay<LOG2N>::HOP;
+    } else {
+        kernel = k_conv_wide<LOG2N>;
+        hop = ConvWide<LOG2N>::HOP;
+    }
+    if constexpr (FORM == CONV_WIDE) {
+        MGX_TRY(allow_lds(k_conv_wide_prep<LOG2N>, lds));
+    } else {
+        MGX_TRY(allow_lds(k_conv_prep<LOG2N>, lds));
+    }
+    MGX_TRY(allow_lds(kernel, lds));
     {
         StageScope scope(h, MGX_STAGE_FILTER_SPECTRA);
-        hipLaunchKernelGGL((k_conv_prep<LOG2N>), dim3(2 * a.parts), dim3(F::T), lds, h->stream, taps_dev,
-                           a.tw, (float2*)h->filt.p, a.parts, gain_ptr, gain);
+        if constexpr (FORM == CONV_WIDE) {
+            hipLaunchKernelGGL(k_conv_wide_prep<LOG2N>, dim3(2), dim3(F::T), lds, h->stream, taps_dev, a.tw,
+                               (float2*)h->filt.p, gain_ptr, gain);
+        } else {
+            hipLaunchKernelGGL(k_conv_prep<LOG2N>, dim3(2 * a.parts), dim3(F::T), lds, h->stream, taps_dev, a.tw,
+                               (float2*)h->filt.p, a.parts, gain_ptr, gain);
+        }
     }
     HIP_TRY(hipGetLastError());
-    a.npairs = (a.n + ConvDelay<LOG2N>::HOP - 1) / ConvDelay<LOG2N>::HOP;
+    a.npairs = (a.n + hop - 1) / hop;
     MGX_TRY(ensure(h, h->block_peak, (size_t)a.npairs * sizeof(float)));
     a.pair_peak = (float*)h->block_peak.p;
-    a.queue = nullptr;
-    int dev_cus = 256;
-    HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const int per_cu = std::max(1, std::min(2048 / F::T, (int)((size_t)160 * 1024 / lds)));
-    const long long cap = (long long)dev_cus * per_cu;
-    a.run = (int)std::max<long long>(1, (a.npairs + cap - 1) / cap);
-    const unsigned grid = (unsigned)((a.npairs + a.run - 1) / a.run);
+    const long long fit = (long long)h->cus * workgroups_per_cu(F::T, lds);
+    unsigned grid;
+    if constexpr (FORM == CONV_QUEUE) {
+        if (!h->conv_queue.p) {                  // zero once: every launch leaves the counters at zero
+            MGX_TRY(ensure(h, h->conv_queue, 64));
+            HIP_TRY(hipMemsetAsync(h->conv_queue.p, 0, 64, h->stream));
+        }
+        a.queue = (unsigned*)h->conv_queue.p;
+        grid = (unsigned)(((std::min(a.npairs, fit) + 7) / 8) * 8);
+    } else if constexpr (FORM == CONV_DELAY) {
+        a.run = (int)std::max<long long>(1, (a.npairs + fit - 1) / fit);
+        grid = (unsigned)((a.npairs + a.run - 1) / a.run);
+    } else {
+        grid = (unsigned)std::min(a.npairs, fit);
+    }
     {
         StageScope scope(h, MGX_STAGE_CONVOLVE);
-        hipLaunchKernelGGL((k_conv_delay<LOG2N>), dim3(grid), dim3(F::T), lds, h->stream, a);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(F::T), lds, h->stream, a);
     }
     HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// F taps on N = 4F blocks (conv_wide_kernel.h; F = 4096 on N = 16384, one workgroup per CU, blocks dealt round-robin).
-// a.npairs counts blocks of 3N/4 frames on return.
-template <int LOG2N>
-static int launch_conv_wide(mgx_handle* h, Conv2Args a, const float* taps_dev, double gain, const double* gain_ptr) {
-    using F = Fft2<LOG2N>;
-    const size_t lds = conv_lds_bytes<LOG2N>();
-    MGX_TRY((allow_lds(k_conv_wide_prep<LOG2N>, lds)));
-    MGX_TRY((allow_lds(k_conv_wide<LOG2N>, lds)));
-    {
-        StageScope scope(h, MGX_STAGE_FILTER_SPECTRA);
-        hipLaunchKernelGGL((k_conv_wide_prep<LOG2N>), dim3(2), dim3(F::T), lds, h->stream, taps_dev, a.tw,
-                           (float2*)h->filt.p, gain_ptr, gain);
-    }
-    HIP_TRY(hipGetLastError());
-    a.parts = 1;
-    a.h_mid = (const float2*)h->filt.p;
-    a.h_side = (const float2*)h->filt.p + F::N;
-    a.npairs = (a.n + ConvWide<LOG2N>::HOP - 1) / ConvWide<LOG2N>::HOP;
-    MGX_TRY(ensure(h, h->block_peak, (size_t)a.npairs * sizeof(float)));
-    a.pair_peak = (float*)h->block_peak.p;
-    a.queue = nullptr;
-    int dev_cus = 256;
-    HIP_TRY(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    const int per_cu = std::max(1, std::min(2048 / F::T, (int)((size_t)160 * 1024 / lds)));
-    const unsigned grid = (unsigned)std::min<long long>(a.npairs, (long long)dev_cus * per_cu);
-    {
-        StageScope scope(h, MGX_STAGE_CONVOLVE);
-        hipLaunchKernelGGL((k_conv_wide<LOG2N>), dim3(grid), dim3(F::T), lds, h->stream, a);
-    }
-    HIP_TRY(hipGetLastError());
+    *blocks = a.npairs;
     return 0;
 }
 
@@ -919,6 +876,7 @@ static int launch_conv_wide(mgx_handle* h, Conv2Args a, const float* taps_dev, d
 // per channel and 8192 output frames, 325 flop per frame and channel; K/2 + 1 of 16384 points per 16384
 // frames are 210.)
 constexpr int LONG_FIR_LOG2N = 14;
+constexpr int WIDE_LOG2N = 14;                                  // CONV_WIDE: 4096 taps on 16384-point blocks
 static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const float* taps_dev, double gain,
                     float* y, float* ymid, long long* npairs_out, const double* gain_ptr = nullptr) {
     const int l = ilog2_exact(taps);
@@ -935,29 +893,13 @@ static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const 
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    {
-        // 4096 taps (the reference's default fft_size) on 16384-point blocks, three quarters of a block fresh output
-        if (taps == 4096 && !h->no_conv_wide) {
-            constexpr int WIDE = 14;
-            MGX_TRY(ensure(h, h->filt, 2 * ((size_t)1 << WIDE) * sizeof(float2)));
-            Conv2Args a;
-            a.x = reinterpret_cast<const float2*>(x);
-            a.n = n;
-            a.y = reinterpret_cast<float2*>(y);
-            a.ymid = ymid;
-            a.run = 0;
-            MGX_TRY(get_twiddles(h, WIDE, &a.tw));
-            if (npairs_out) *npairs_out = (n + ConvWide<WIDE>::HOP - 1) / ConvWide<WIDE>::HOP;
-            return launch_conv_wide<WIDE>(h, a, taps_dev, gain, gain_ptr);
-        }
-    }
-    int log2b = l + 1;
-    if (log2b > 14) log2b = LONG_FIR_LOG2N;
+    // 4096 taps (the reference's default fft_size) on 16384-point blocks, three quarters of a block fresh output
+    const bool wide = taps == 4096 && !h->no_conv_wide;
     // (N = 4F -- 4096 taps on 16384-point blocks, 187 instead of 260 flop per frame -- was retried in round 4 with the
     // register diet the kernel has had since round 1: 264 against 148 us, profiles/r04_g_conv_n4f.txt)
+    const int log2b = wide ? WIDE_LOG2N : std::min(l + 1, LONG_FIR_LOG2N);
     const size_t nb = (size_t)1 << log2b;
-    const int parts = (int)((size_t)2 * taps / nb);
-    const long long pair_frames = (long long)nb;
+    const int parts = wide ? 1 : (int)((size_t)2 * taps / nb);
     MGX_TRY(ensure(h, h->filt, 2 * (size_t)parts * nb * sizeof(float2)));
     Conv2Args a;
     a.x = reinterpret_cast<const float2*>(x);
@@ -967,22 +909,26 @@ static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const 
     a.h_mid = (const float2*)h->filt.p;
     a.h_side = (const float2*)h->filt.p + (size_t)parts * nb;
     a.parts = parts;
-    a.npairs = (n + pair_frames - 1) / pair_frames;
-    a.pair_peak = nullptr;
-    MGX_TRY(get_twiddles(h, log2b, &a.tw));
+    a.queue = nullptr;
     a.run = 0;
-    if (parts == 2 && !h->no_conv_delay) {
-        if (npairs_out) *npairs_out = (n + (long long)nb / 2 - 1) / ((long long)nb / 2);
-        return launch_conv_delay<LONG_FIR_LOG2N>(h, a, taps_dev, gain, gain_ptr);
-    }
-    if (npairs_out) *npairs_out = a.npairs;
-    if (parts > 1) return launch_conv<LONG_FIR_LOG2N, true>(h, a, taps_dev, gain, gain_ptr);
-    switch (log2b) {
-#define CASE(L) case L: return launch_conv<L, false>(h, a, taps_dev, gain, gain_ptr);
-        CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14)
+    MGX_TRY(get_twiddles(h, log2b, &a.tw));
+    long long blocks = 0;
+    if (wide) {
+        MGX_TRY((launch_conv<WIDE_LOG2N, CONV_WIDE>(h, a, taps_dev, gain, gain_ptr, &blocks)));
+    } else if (parts == 2 && !h->no_conv_delay) {
+        MGX_TRY((launch_conv<LONG_FIR_LOG2N, CONV_DELAY>(h, a, taps_dev, gain, gain_ptr, &blocks)));
+    } else if (parts > 1) {
+        MGX_TRY((launch_conv<LONG_FIR_LOG2N, CONV_QUEUE, true>(h, a, taps_dev, gain, gain_ptr, &blocks)));
+    } else {
+        switch (log2b) {
+#define CASE(L) case L: MGX_TRY((launch_conv<L, CONV_QUEUE>(h, a, taps_dev, gain, gain_ptr, &blocks))); break;
+            CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14)
 #undef CASE
-        default: return fail(MGX_ERR_UNSUPPORTED, "FIR length not supported by the convolution kernel");
+            default: return fail(MGX_ERR_UNSUPPORTED, "FIR length not supported by the convolution kernel");
+        }
     }
+    if (npairs_out) *npairs_out = blocks;
+    return 0;
 }
 
 static int clipped_chunks(int divisions) { return std::max(1, std::min(1024, (2048 + divisions - 1) / divisions)); }
@@ -1002,11 +948,8 @@ static int run_clipped_sumsq(mgx_handle* h, const float* mid, long long piece, i
 // (blocks per limiter chunk: the rule of host_params.h.  Chunks of 512 blocks were built and measured in round 6 for
 // 96 kHz, where the halos eat a quarter of a 256-block chunk: 221 us against 204 (and 306 for 1024 blocks), 84 B of
 // scratch at the 128 registers two workgroups per CU leave -- profiles/r06_b_*; removed.)
-static int limiter_state(mgx_handle* h, long long n, const mgx_config* cfg, unsigned long long** published,
+static int limiter_state(mgx_handle* h, long long n, const LimiterParams& lp, unsigned long long** published,
                          long long* words, int** ticket) {
-    LimiterParams lp;
-    const std::string err = limiter_params(*cfg, lp);
-    if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     const long long nchunks = (n + lp.geo.chunk - 1) / lp.geo.chunk;
     MGX_TRY(ensure(h, h->lim_published, (size_t)limiter_words(lp, nchunks) * sizeof(unsigned long long)));
     MGX_TRY(ensure_ctrl(h));
@@ -1064,14 +1007,10 @@ static int launch_limiter(mgx_handle* h, const LimiterArgs& a, int threads) {
 }
 
 // everything of a limiter launch but the look-back words, ticket and error flag
-static int limiter_args(mgx_handle* h, const float* y, long long n, const mgx_config* cfg, const double* gain_dev,
-                        const double* post_dev, const int* active_dev, float* out, LimiterArgs& a, int* threads,
-                        LimiterParams& lp) {
-    const std::string err = limiter_params(*cfg, lp);
-    if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
+static int limiter_args(mgx_handle* h, const float* y, long long n, const LimiterParams& lp, double threshold,
+                        const double* gain_dev, const double* post_dev, const int* active_dev, float* out, LimiterArgs& a) {
     if (n < 8) return fail(MGX_ERR_ARGUMENT, "limiter input too short");
-    limiter_fill(lp, (float)cfg->threshold, a);
-    *threads = lp.threads;
+    limiter_fill(lp, (float)threshold, a);
     a.y = reinterpret_cast<const float2*>(y);
     a.n = n;
     a.out = reinterpret_cast<float2*>(out);
@@ -1097,12 +1036,11 @@ static int limiter_args(mgx_handle* h, const float* y, long long n, const mgx_co
 }
 
 // preset_done: the caller's previous kernel has already preset the look-back words and the ticket
-static int run_limiter(mgx_handle* h, const float* y, long long n, const mgx_config* cfg, const double* gain_dev,
-                       const double* post_dev, const int* active_dev, float* out, bool preset_done = false) {
+static int run_limiter(mgx_handle* h, const float* y, long long n, const LimiterParams& lp, double threshold,
+                       const double* gain_dev, const double* post_dev, const int* active_dev, float* out,
+                       bool preset_done = false) {
     LimiterArgs a;
-    LimiterParams lp;
-    int threads = 256;
-    MGX_TRY(limiter_args(h, y, n, cfg, gain_dev, post_dev, active_dev, out, a, &threads, lp));
+    MGX_TRY(limiter_args(h, y, n, lp, threshold, gain_dev, post_dev, active_dev, out, a));
     // published words preset to "unpublished", ticket and error zeroed, every launch
     const size_t pub_bytes = (size_t)limiter_words(lp, a.nchunks) * sizeof(unsigned long long);
     MGX_TRY(ensure(h, h->lim_published, pub_bytes));
@@ -1127,7 +1065,7 @@ static int run_limiter(mgx_handle* h, const float* y, long long n, const mgx_con
     if (shared && chain.last && chain.last != h->lim_done) HIP_TRY(hipStreamWaitEvent(h->stream, chain.last, 0));
     int rc = 0;
     switch (lp.general) {
-        case 0: rc = launch_limiter(h, a, threads); break;
+        case 0: rc = launch_limiter(h, a, lp.threads); break;
         case 2: rc = launch_limiter_general<2>(h, a, lp); break;
         default: rc = launch_limiter_general<3>(h, a, lp); break;
     }
@@ -1287,6 +1225,7 @@ int mgx_create(int device, mgx_handle** out) {
     HIP_TRY(hipSetDevice(device));
     mgx_handle* h = new mgx_handle();
     h->device = device;
+    HIP_TRY(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device));
     // the environment switches, read once here: a host thread's setenv cannot race a running call
     h->no_conv_wide = env_flag("MGX_NO_CONV_WIDE");
     h->no_conv_delay = env_flag("MGX_NO_CONV_DELAY");
@@ -1332,16 +1271,6 @@ int mgx_destroy(mgx_handle* h) {
     }
     if (h->lim_done) hipEventDestroy(h->lim_done);
     if (h->comm) ncclCommDestroy(h->comm);
-    DevBuf* bufs[] = {&h->y, &h->mid, &h->block_peak, &h->filt, &h->taps, &h->partial, &h->cstate,
-                      &h->scalars, &h->lim_published, &h->lim_ctrl, &h->lim_weights, &h->lim_tables, &h->fir_robust, &h->peak_words, &h->fir_scratch, &h->round_ctr, &h->tail_gains, &h->band, &h->band_info,
-                      &h->conv_queue};
-    for (DevBuf* b : bufs)
-        if (b->p) hipFree(b->p);
-    for (TrackWork& w : h->track) {
-        DevBuf* tb[] = {&w.wg_sumsq, &w.wg_peak, &w.wg_spec, &w.wg_pack, &w.stats, &w.rms, &w.loud, &w.avg, &w.part};
-        for (DevBuf* b : tb)
-            if (b->p) hipFree(b->p);
-    }
     for (auto& kv : h->twiddles) hipFree(kv.second);
     if (h->pinned) hipHostFree(h->pinned);
     if (h->error_host) hipHostFree(h->error_host);
@@ -1351,7 +1280,7 @@ int mgx_destroy(mgx_handle* h) {
         for (hipEvent_t e : pair)
             if (e) hipEventDestroy(e);
     hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                               // (and with it every DevBuf of the handle and its tracks)
     return 0;
 }
 
@@ -1551,9 +1480,13 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
         HIP_TRY(hipStreamSynchronize(h->stream));
         MGX_TRY(check_device_error(h));
     }
+    LimiterParams lp;
+    const std::string err = limiter_params(*cfg, lp);
+    if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     for (int attempt = 0;; ++attempt) {
         const bool tickets_before = h->limiter_tickets;
-        MGX_TRY(run_limiter(h, x_dev, n, cfg, &cs->gain, (const double*)h->scalars.p, &cs->limiter_active, out_dev));
+        MGX_TRY(run_limiter(h, x_dev, n, lp, cfg->threshold, &cs->gain, (const double*)h->scalars.p, &cs->limiter_active,
+                            out_dev));
         HIP_TRY(hipMemcpyAsync(&host_cs, cs, sizeof(host_cs), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         const int rc = check_device_error(h);
@@ -1679,11 +1612,6 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     float* result_no_limiter_dev = c.out[1];
     float* result_no_limiter_normalized_dev = c.out[2];
     const int f = cfg->fft_size;
-    if (result_dev) {               // validate limiter parameters before any work is queued
-        LimiterParams lp;
-        const std::string err = limiter_params(*cfg, lp);
-        if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
-    }
     // stage 1 (stages.py:38-104): both tracks analysed in one pass each
     TrackWork& tw = h->track[0];
     TrackWork& rw = h->track[1];
@@ -1750,7 +1678,7 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
         MGX_TRY(ensure_ctrl(h));
         ra.error = h->error_dev;
         const size_t lds_step = (size_t)(64 + tw.divisions + (size_t)ra.divisions * ra.chunks) * sizeof(double);
-        if (lds_step > (size_t)150 * 1024)
+        if (lds_step > LDS_PER_WORKGROUP_MAX)
             return fail(MGX_ERR_UNSUPPORTED, "too many analysis pieces for the level-correction kernel's LDS");
         MGX_TRY(allow_lds(k_correction_round, lds_step));
         const int rounds = cfg->rms_correction_steps;
@@ -1758,20 +1686,15 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
         ra.lim_words = 0;
         ra.lim_ticket = nullptr;
         ra.tail_gains = use_tail ? (unsigned long long*)h->tail_gains.p : nullptr;
-        auto with_final = [&](RoundArgs& r) -> int {          // the launch that runs the last round
-            r.final_peaks = (const float*)h->block_peak.p;
-            return 0;
-        };
         if (rounds >= 1) {                                    // round 0 streams the mid plane and builds the band lists
             RoundArgs r0 = ra;
-            r0.final_peaks = nullptr;
+            r0.final_peaks = rounds == 1 ? (const float*)h->block_peak.p : nullptr;    // (the launch of the last round)
             r0.build_band = 1;
             r0.step = 0;
             if (result_dev) {     // the limiter's look-back words are preset by this grid: a thousand workgroups, two words a thread
-                MGX_TRY(limiter_state(h, n_target, cfg, &r0.lim_published, &r0.lim_words, &r0.lim_ticket));
+                MGX_TRY(limiter_state(h, n_target, c.lp, &r0.lim_published, &r0.lim_words, &r0.lim_ticket));
                 limiter_preset = true;
             }
-            if (rounds == 1) MGX_TRY(with_final(r0));
             hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, r0);
         }
         if (rounds > 1 && !use_tail) {
@@ -1781,8 +1704,7 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
                 RoundArgs rr = ra;
                 rr.build_band = 0;
                 rr.step = r;
-                rr.final_peaks = nullptr;
-                if (r == rounds - 1) MGX_TRY(with_final(rr));
+                rr.final_peaks = r == rounds - 1 ? (const float*)h->block_peak.p : nullptr;
                 hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, rr);
             }
         }
@@ -1790,10 +1712,10 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
             RoundArgs rt = ra;
             rt.build_band = 0;
             rt.step = 1;
-            MGX_TRY(with_final(rt));
+            rt.final_peaks = (const float*)h->block_peak.p;
             const int groups = tail_groups;
             const size_t lds_tail = correction_tail_lds_bytes(ra.divisions, groups, ra.chunks);
-            if (lds_tail > (size_t)150 * 1024)
+            if (lds_tail > LDS_PER_WORKGROUP_MAX)
                 return fail(MGX_ERR_UNSUPPORTED, "too many analysis pieces for the level-correction kernel's LDS");
             MGX_TRY(allow_lds(k_correction_tail, lds_tail));
             // (+ 1: the deciding workgroup)
@@ -1817,8 +1739,8 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     if (result_dev) {
         StageScope scope(h, MGX_STAGE_LIMIT);
         const double* post = &((const TrackStats*)rw.stats.p)->amplitude_c;
-        MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, cfg, &cs->gain, post, &cs->limiter_active, result_dev,
-                            limiter_preset));
+        MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, c.lp, cfg->threshold, &cs->gain, post, &cs->limiter_active,
+                            result_dev, limiter_preset));
     }
     return 0;
 }
@@ -1829,13 +1751,14 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
     if (!h || !target_dev || !reference_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(check_config(cfg));
     HIP_TRY(hipSetDevice(h->device));
-    if (result_dev) {               // validate limiter parameters before any work is queued
-        LimiterParams lp;
+    LimiterParams lp{};
+    if (result_dev) {               // derived (and validated) once, before any work is queued
         const std::string err = limiter_params(*cfg, lp);
         if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     }
     mgx_handle::MasterCall& call = h->last_call;
     call.valid = false;
+    call.lp = std::move(lp);
     call.target = target_dev;
     call.reference = reference_dev;
     call.fir_given = fir_given;

@@ -9,6 +9,7 @@
 // shipped library contains no host implementation of any kernel.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <cmath>
 
@@ -270,6 +271,17 @@ constexpr int bitrev(int v, int bits) {
     int r = 0;
     for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1) << (bits - 1 - i);
     return r;
+}
+
+// LDS of one CU, and the most a launch here gives one workgroup (what a run-time size is checked against)
+constexpr size_t LDS_PER_CU = (size_t)160 * 1024;
+constexpr size_t LDS_PER_WORKGROUP_MAX = (size_t)150 * 1024;
+// workgroups of `threads` threads and `lds` bytes of LDS that fit one CU at once (2048 threads and LDS_PER_CU), at
+// least 1.  Callers apply their own caps.
+constexpr int workgroups_per_cu(int threads, size_t lds) {
+    const int by_lds = (int)(LDS_PER_CU / lds), by_threads = 2048 / threads;
+    const int w = by_lds < by_threads ? by_lds : by_threads;
+    return w < 1 ? 1 : w;
 }
 
 }  // namespace mgx

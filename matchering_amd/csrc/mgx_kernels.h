@@ -214,10 +214,8 @@ __device__ __forceinline__ int opaque(int v) {
 // register budget the kernel is compiled for
 template <int LOG2N>
 constexpr int conv_workgroups_per_cu() {
-    constexpr int by_lds = (int)((size_t)160 * 1024 / conv_lds_bytes<LOG2N>());
-    constexpr int by_threads = 2048 / Fft2<LOG2N>::T;
-    constexpr int w = by_lds < by_threads ? by_lds : by_threads;
-    return w < 1 ? 1 : (w > 2 ? 2 : w);             // more than two co-resident transforms do not pay
+    constexpr int w = workgroups_per_cu(Fft2<LOG2N>::T, conv_lds_bytes<LOG2N>());
+    return w > 2 ? 2 : w;                            // more than two co-resident transforms do not pay
 }
 template <int LOG2N>
 constexpr int conv_waves_per_simd() {
@@ -563,8 +561,8 @@ constexpr size_t analysis_lds_bytes() {
 constexpr int ANALYZE_MAX_WGS = 8;      // workgroups per CU at most (host: analysis_workgroups_per_cu)
 template <int LOG2N>
 constexpr int analysis_waves_per_simd() {
-    constexpr int by_lds = (int)((size_t)160 * 1024 / analysis_lds_bytes<LOG2N>());
-    constexpr int wgs = by_lds < ANALYZE_MAX_WGS ? by_lds : ANALYZE_MAX_WGS;
+    constexpr int fit = workgroups_per_cu(Fft2<LOG2N>::T, analysis_lds_bytes<LOG2N>());
+    constexpr int wgs = fit < ANALYZE_MAX_WGS ? fit : ANALYZE_MAX_WGS;
     constexpr int w = wgs * (Fft2<LOG2N>::T / 64) / 4;
     return w < 1 ? 1 : (w > 8 ? 8 : w);
 }
@@ -1734,25 +1732,6 @@ __global__ __launch_bounds__(256) void k_clipped_sumsq(const float* mid, long lo
     }
     const double s = block_sum<256>(acc, scratch);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-// one round of stages.py:149-168 on the partial sums
-__global__ __launch_bounds__(1024) void k_correction_step(const double* partial, int chunks, int divisions,
-                                                          long long piece, const double* reference_match_rms,
-                                                          double eps, CorrectionState* cs) {
-    MGX_LDS;
-    double* red = reinterpret_cast<double*>(mgx_smem);
-    double* sums = red + 64;
-    piece_sums_to_lds(partial, chunks, divisions, sums);
-    double avg, match;
-    int count;
-    decide_loud<1024>(sums, divisions, piece, 1.0, red, nullptr, nullptr, avg, match, count);
-    if (threadIdx.x == 0) {
-        const double c = *reference_match_rms / fmax(eps, match);      // match_levels.py:106-111
-        if (cs->steps_done < 16) cs->coeffs[cs->steps_done] = c;
-        cs->steps_done += 1;
-        cs->gain *= c;
-    }
 }
 
 // One round of stages.py:149-168 in ONE launch: every workgroup sums its chunk of
