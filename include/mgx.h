@@ -190,6 +190,26 @@ int mgx_peak_count(mgx_handle* h, const float* x_dev, int64_t samples, double* p
 int mgx_pcm_decode(mgx_handle* h, const void* pcm_dev, int64_t samples, int32_t bits, float* out_dev);
 int mgx_pcm_encode(mgx_handle* h, const float* x_dev, int64_t samples, int32_t bits, void* pcm_dev);
 
+/* Sample-rate conversion in HBM: matchering/checker.py:30-45 (`resampy.resample(array, sample_rate,
+ * required_sample_rate, axis=0)`, filter kaiser_best) for a track that mgx_pcm_decode has just left on the device, so
+ * that a file at another rate than Config.internal_sample_rate never becomes a float64 array on the host.  x_dev:
+ * (n, channels) float32, one or two channels; out_dev: (n_out, 2) float32 -- a mono track comes out as two equal
+ * columns (dsp.py:45-46) -- with n_out = int(n * (rate_out / rate_in)), known before the launch: with out_dev == NULL
+ * the call only reports it (and needs no handle), so that the caller can allocate.  The sum is resampy's, phase by
+ * phase with exact integer phase arithmetic, samples and weights in float64, rounded once to float32 at the store.
+ * Queued on the handle's stream.  The weights of a rate pair are designed and uploaded on the handle's first
+ * conversion between those rates and kept.  MGX_ERR_ARGUMENT: channels other than 1 or 2, a rate <= 0, rate_in ==
+ * rate_out, out_capacity_frames < n_out.  MGX_ERR_UNSUPPORTED (the host converts such a file, as it did before): a
+ * ratio of more than 4096 phases (44100 -> 44101), an output rate so far below the input rate that 256 outputs reach
+ * more than 7680 input frames, more than 64 MiB of weights.  n_out == 0 succeeds and launches nothing.
+ * mgx_resample_plan: the device address and shape ([row_entries][phases] float64) of the weights kept for a rate
+ * pair, and how many plans this handle has designed and uploaded so far: a second conversion between the same rates
+ * changes neither. */
+int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels, int32_t rate_in, int32_t rate_out,
+                 float* out_dev, int64_t out_capacity_frames, int64_t* n_out);
+int mgx_resample_plan(mgx_handle* h, int32_t rate_in, int32_t rate_out, void** weights_dev, int32_t* phases,
+                      int32_t* row_entries, int64_t* designed);
+
 /* Album mode (the use of the FIR broadcast): stages.main with the matching-EQ FIR
  * GIVEN instead of designed from this pair's spectra -- `fir_dev` = [2][fft_size] float32 in HBM, mid
  * taps then side taps, e.g. the table mgx_last_fir returns on the rank that designed it, after

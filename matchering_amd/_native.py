@@ -108,6 +108,10 @@ SYMBOLS = {
     "mgx_peak_count": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, c_double_p, ctypes.POINTER(ctypes.c_int64)]),
     "mgx_pcm_decode": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, _VP]),
     "mgx_pcm_encode": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, _VP]),
+    "mgx_resample": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _VP,
+                                    ctypes.c_int64, c_int64_p]),
+    "mgx_resample_plan": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_VP), c_int32_p, c_int32_p,
+                                         c_int64_p]),
     "mgx_window_energy": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_double_p,
                                          ctypes.c_int64, c_int64_p]),
     "mgx_preview_cut": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -127,6 +131,7 @@ STAGES = ("analyze", "design_fir", "filter_spectra", "convolve", "correct_levels
 
 
 ERR_RETRY = -6          # enum mgx_status MGX_ERR_RETRY (include/mgx.h)
+ERR_UNSUPPORTED = -4    # ... MGX_ERR_UNSUPPORTED
 
 
 class MgxError(RuntimeError):

@@ -336,24 +336,55 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     return results
 
 
-def _peaks_on_the_lane(target, device_index, lane, config, master):
-    """The part of checker.check that ``_load_job`` left out for an integer PCM target: upload it on the
-    lane's device, take count_max_peaks there (mgx_peak_count), warn as the reference would; the resident
-    frames go on to stages.main.  With a stand-in for the GPU the statistics are taken on the host."""
+class _Later:
+    """What ``_load_job`` left to the lane that masters the job, per track the file's rate when the track is still
+    as its file holds it (None: it is the final track already)."""
+
+    def __init__(self, target_rate=None, reference_rate=None, equality=False):
+        self.target_rate, self.reference_rate, self.equality = target_rate, reference_rate, equality
+
+
+def _on_the_lane(target, reference, later, device_index, lane, config, master):
+    """The part of checker.check that ``_load_job`` left out: upload the tracks it kept as their files hold them on
+    the lane's device, convert them there when they are mono or off-rate (``Device.track_frames``, queued on the
+    lane's handle), take the target's count_max_peaks there (mgx_peak_count) and warn as the reference would; the
+    resident frames go on to stages.main.  With a stand-in for the GPU the statistics are taken on the host."""
     from .audio_io import unpack24
-    from .checker import count_max_peaks, peak_warnings
+    from .checker import check_equality, count_max_peaks, peak_warnings
 
     if master is not None:
         peak_warnings(count_max_peaks(unpack24(target) if target.dtype == np.uint8 else target), config)
-        return target
-    from .device import DeviceFrames
-
+        return target, reference
     dev = lane_device(device_index, lane)
-    with dev.lock:
-        frames = DeviceFrames(dev.upload_frames(target), target.shape[0])
-        peaks = dev.peak_count(frames, 2 * target.shape[0])
-    peak_warnings(peaks, config)
-    return frames
+    internal = config.internal_sample_rate
+    on_device = [None, None]
+    try:
+        with dev.lock:
+            for slot, (audio, rate) in enumerate(((target, later.target_rate), (reference, later.reference_rate))):
+                if rate is not None:
+                    on_device[slot] = dev.track_frames(audio, rate, internal)
+            if on_device[0] is not None:
+                peaks = dev.peak_count(on_device[0], 2 * on_device[0].frames)
+        if later.equality:
+            check_equality(target, reference, [frames if frames is not None and _changes(audio, rate, internal) else None
+                                               for frames, audio, rate in ((on_device[0], target, later.target_rate),
+                                                                           (on_device[1], reference, later.reference_rate))])
+        if on_device[0] is not None:
+            peak_warnings(peaks, config)
+    except Exception:
+        for frames in on_device:
+            if frames is not None:
+                frames.release()
+        raise
+    return (on_device[0] if on_device[0] is not None else target,
+            on_device[1] if on_device[1] is not None else reference)
+
+
+def _changes(audio, rate, internal):
+    """Whether the device changes the track's rate or channels (its host array is then not the final track)."""
+    from .audio_io import pcm_channels
+
+    return rate != internal or pcm_channels(audio) != 2
 
 
 def _wanted_encodings(results):
@@ -368,29 +399,57 @@ def _needs_of(results):
             any(not r.use_limiter and r.normalize for r in results))
 
 
-def _load_job(job, config):
+def _load_job(job, config, gpu=False):
     """Load + check both files of a job (core.py:52-74), on a host thread.  Returns (target, reference,
-    deferred): with ``deferred`` the target is integer PCM that goes to the GPU as it is, and its peak
-    statistics (checker.py:118-130) are left to the lane that masters it (``mgx_peak_count``)."""
+    later): with ``later`` (a ``_Later``) a track is still as its file holds it and goes to the GPU that way.  The
+    target's peak statistics (checker.py:118-130) are then left to the lane that masters it (``mgx_peak_count``),
+    and with ``gpu`` so is the conversion of a mono or off-rate track (``device.takes_resident``, the rule
+    ``core.process`` uses): a loader thread never spends seconds in the host resampler while its lane idles."""
     from .audio_io import load, pcm_channels
     from .checker import LATER, check, check_equality
     from .utils import get_temp_folder
 
+    internal = config.internal_sample_rate
     temp_folder = config.temp_folder if config.temp_folder else get_temp_folder(job["results"])
+
+    def on_the_lane(audio, rate):
+        """(the track stays as its file holds it, its final frame count)"""
+        if gpu:
+            from .device import final_frames, takes_resident
+
+            if takes_resident(audio, rate, internal):
+                return True, final_frames(audio, rate, internal)
+            return False, None
+        return ((audio.dtype.kind in "iu" or audio.dtype == np.float32) and pcm_channels(audio) == 2
+                and rate == internal), audio.shape[0]
+
     # (pcm=True: 16/24/32-bit WAVE samples stay integers up to the GPU, as in core.process)
     target, rate_t = load(job["target"], "target", temp_folder, pcm=True)
-    deferred = ((target.dtype.kind in "iu" or target.dtype == np.float32) and pcm_channels(target) == 2
-                and rate_t == config.internal_sample_rate)
-    target, rate_t = check(target, rate_t, config, "target", peaks=LATER if deferred else None)
+    file_rate_t = rate_t
+    deferred, frames_t = on_the_lane(target, rate_t)
+    convert_t = deferred and _changes(target, rate_t, internal)
+    target, rate_t = check(target, rate_t, config, "target", peaks=LATER if deferred else None, on_device=convert_t)
     reference, rate_r = load(job["reference"], "reference", temp_folder, pcm=True)
-    reference, rate_r = check(reference, rate_r, config, "reference")
+    file_rate_r = rate_r
+    convert_r, frames_r = on_the_lane(reference, rate_r)
+    convert_r = convert_r and _changes(reference, rate_r, internal)      # (a reference that is final goes up in stages.main)
+    reference, rate_r = check(reference, rate_r, config, "reference", on_device=convert_r)
+    frames_t = frames_t if convert_t else target.shape[0]
+    frames_r = frames_r if convert_r else reference.shape[0]
+    equality = False
     if not config.allow_equality:
-        check_equality(target, reference)
-    if (not (rate_t == rate_r == config.internal_sample_rate)
-            or not (pcm_channels(target) == pcm_channels(reference) == 2)
-            or not (target.shape[0] > config.fft_size and reference.shape[0] > config.fft_size)):
+        if convert_t or convert_r:
+            equality = frames_t == frames_r        # (tracks of unequal length are not equal; else the lane compares them)
+        else:
+            check_equality(target, reference)
+    if (not (rate_t == rate_r == internal)
+            or not ((convert_t or pcm_channels(target) == 2) and (convert_r or pcm_channels(reference) == 2))
+            or not (frames_t > config.fft_size and frames_r > config.fft_size)):
         raise ModuleError(Code.ERROR_VALIDATION)
-    return target, reference, deferred
+    later = None
+    if deferred or convert_r:
+        later = _Later(file_rate_t if deferred else None, file_rate_r if convert_r else None, equality)
+    return target, reference, later
 
 
 def _save_job(job, triple, config):
@@ -423,13 +482,13 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
             workers = {}
 
             def run(item):
-                index, (target, reference, deferred) = item
+                index, (target, reference, later) = item
                 needs = _needs_of(jobs[index]["results"])
                 key = (needs, _wanted_encodings(jobs[index]["results"]))
                 if key not in workers:
                     workers[key] = _device_worker(device_index, lane, config, needs, master, key[1])
-                if deferred:
-                    target = _peaks_on_the_lane(target, device_index, lane, config, master)
+                if later is not None:
+                    target, reference = _on_the_lane(target, reference, later, device_index, lane, config, master)
                 return workers[key]((target, reference))
             return run
 
@@ -449,13 +508,13 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                 future.add_done_callback(lambda _f: unsaved.release())
                 savers.append(future)
 
-        ahead = {k: io.submit(_load_job, jobs[i], config) for k, i in enumerate(mine[:io_threads])}
+        ahead = {k: io.submit(_load_job, jobs[i], config, master is None) for k, i in enumerate(mine[:io_threads])}
         nxt = len(ahead)
         try:
             for k, i in enumerate(mine):
                 arrays = ahead.pop(k).result()            # (popped: the decoded arrays live on only in the job)
                 if nxt < len(mine):
-                    ahead[nxt] = io.submit(_load_job, jobs[mine[nxt]], config)
+                    ahead[nxt] = io.submit(_load_job, jobs[mine[nxt]], config, master is None)
                     nxt += 1
                 pool.submit(i, (i, arrays), done)
                 del arrays

@@ -2,10 +2,12 @@
 stereo, resampling to ``config.internal_sample_rate``, clipping / limiter detection on the target,
 and the "target equals reference" guard.  Host numpy: none of this is on the timed path.
 
-Resampling: the reference calls ``resampy.resample`` (Kaiser-windowed sinc table, ``kaiser_best``).  ``resampy`` is
-used when it is importable; otherwise ``matchering_amd.resample`` does the rate change -- the same algorithm
-restated (parity with the package unpinned: it is not in the build image), only reached when a file's rate
-differs from the internal rate.
+Resampling: the reference calls ``resampy.resample`` (Kaiser-windowed sinc table, ``kaiser_best``).  With a GPU the
+loaders convert an off-rate track there (``mgx_resample``, ``device.takes_resident``) and ``check(..., on_device=True)``
+does everything but the conversion.  The host form below is the fallback -- no GPU, 32-bit integer and float64 files,
+ratios the library refuses -- and the reference the device is tested against: ``resampy`` when it is importable,
+otherwise ``matchering_amd.resample``, the same algorithm restated (parity with the package unpinned: it is not in
+the build image).
 """
 
 
@@ -70,13 +72,19 @@ def peak_warnings(peaks, config: Config) -> None:
             warning(Code.WARNING_TARGET_LIMITER_IS_APPLIED)
 
 
-def check(array: np.ndarray, sample_rate: int, config: Config, name: str, peaks=None):
+def check(array: np.ndarray, sample_rate: int, config: Config, name: str, peaks=None, on_device=False):
     """checker.py:90-137: returns the validated ``(array (n, 2), internal_sample_rate)``.  ``array`` may be
     integer PCM as a file holds it (audio_io); ``peaks`` = ``count_max_peaks`` of the track when the caller
     has it already (``process`` takes it on the GPU, ``mgx_peak_count``) -- the samples are then not read --
-    or ``LATER`` when it will call ``peak_warnings`` itself."""
+    or ``LATER`` when it will call ``peak_warnings`` itself.  ``on_device=True``: the track is brought to two
+    channels at the internal rate on the device (``mgx_resample``), so everything here happens but that: the
+    length limits against the file's own rate and length, the channel count, the same log codes in the same
+    order, the peak warnings from ``peaks`` (the converted track's statistics, or ``LATER``); the samples are not
+    read and ``array`` comes back as it was given."""
     name = name.upper()
     target = name == "TARGET"
+    if on_device and target and peaks is None:
+        raise ValueError("check(on_device=True) needs the converted target's peak statistics, or LATER")
     length = array.shape[0]
     debug(f"{name}: {length} frames = {time_str(length, sample_rate)}")
     if length > config.max_length * sample_rate:
@@ -88,13 +96,14 @@ def check(array: np.ndarray, sample_rate: int, config: Config, name: str, peaks=
 
     channels = pcm_channels(array)
     converting = channels != 2 or sample_rate != config.internal_sample_rate
-    if converting and peaks is LATER:
+    if converting and peaks is LATER and not on_device:
         peaks = None                                                    # (taken below, on the converted track)
-    if array.dtype == np.uint8 and (converting or (target and peaks is None)):
+    if not on_device and array.dtype == np.uint8 and (converting or (target and peaks is None)):
         array = unpack24(array)                                         # packed samples: only as they are, or not
     if channels == 1:
         info(Code.INFO_TARGET_IS_MONO if target else Code.INFO_REFERENCE_IS_MONO)
-        array = np.repeat(array, repeats=2, axis=1)                     # dsp.py:45-46
+        if not on_device:
+            array = np.repeat(array, repeats=2, axis=1)                 # dsp.py:45-46
     elif channels != 2:
         raise ModuleError(Code.ERROR_TARGET_NUM_OF_CHANNELS_IS_EXCEEDED if target
                           else Code.ERROR_REFERENCE_NUM_OF_CHANNELS_IS_EXCEEDED)
@@ -103,8 +112,9 @@ def check(array: np.ndarray, sample_rate: int, config: Config, name: str, peaks=
         debug(f"{name}: converting {sample_rate} Hz -> {config.internal_sample_rate} Hz")
         # float64 like the arrays soundfile hands the reference's resampler (checker.py:42), also for files
         # that arrive as float32 (FLOAT WAVE, 8-bit PCM)
-        array = _resample(np.asarray(pcm_to_float(array, np.float64), dtype=np.float64), sample_rate,
-                          config.internal_sample_rate)
+        if not on_device:
+            array = _resample(np.asarray(pcm_to_float(array, np.float64), dtype=np.float64), sample_rate,
+                              config.internal_sample_rate)
         if target:
             warning(Code.WARNING_TARGET_IS_RESAMPLED)
         else:
@@ -116,9 +126,19 @@ def check(array: np.ndarray, sample_rate: int, config: Config, name: str, peaks=
     return array, sample_rate
 
 
-def check_equality(target: np.ndarray, reference: np.ndarray) -> None:
+def check_equality(target: np.ndarray, reference: np.ndarray, converted=(None, None)) -> None:
     """checker.py:140-142: numpy.allclose of the two tracks, evaluated a block at a time so that tracks
-    that differ -- the normal case -- are told apart after the first block."""
+    that differ -- the normal case -- are told apart after the first block.  ``converted``: per track, the
+    ``DeviceFrames`` that hold it when ``check(on_device=True)`` left its conversion to the device: tracks of
+    unequal length are told apart without a copy, otherwise the converted frames are downloaded."""
+    if any(frames is not None for frames in converted):
+        lengths = [array.shape[0] if frames is None else frames.frames
+                   for array, frames in zip((target, reference), converted)]
+        if lengths[0] != lengths[1]:
+            return
+        target, reference = (
+            frames.host() if frames is not None else unpack24(array) if array.dtype == np.uint8 else array
+            for array, frames in zip((target, reference), converted))
     if target.shape != reference.shape:
         return
     step = 1 << 18

@@ -72,40 +72,45 @@ def _gpu():
 
 def _read_pair(target_path, reference_path, config, temp_folder):
     """Load and check both tracks (core.py:52-74); raises ModuleError with the reference's codes.  Integer
-    PCM and float32 tracks that need no channel or rate conversion go to the GPU at once: they are decoded
-    there, the target's peak statistics (checker.py:118-130) are taken there, and ``main`` receives them
-    resident."""
-    from .device import DeviceFrames
+    PCM and float32 tracks go to the GPU at once, as their files hold them (``device.takes_resident``): they are
+    decoded there, brought to two channels at the internal rate there when they are mono or off-rate
+    (``mgx_resample``), the target's peak statistics (checker.py:118-130) are taken there, and ``main`` receives
+    them resident.  ``check`` does everything else, for every track."""
+    from .device import takes_resident
 
     dev = _gpu()
-    tracks, resident = [], []
+    internal = config.internal_sample_rate
+    tracks, resident, converted = [], [], []
     for path, role in ((target_path, "target"), (reference_path, "reference")):
         audio, rate = load(path, role, temp_folder, pcm=True)    # 16/24/32-bit WAVE: decoded on the GPU
         peaks, frames = None, None
-        # (integer PCM, or float32 frames as a FLOAT file holds them)
-        direct = (dev is not None and (audio.dtype.kind in "iu" or audio.dtype == np.float32)
-                  and pcm_channels(audio) == 2 and rate == config.internal_sample_rate and audio.shape[0] > 0)
-        if direct:
+        if dev is not None and takes_resident(audio, rate, internal):
             with dev.lock:
-                frames = DeviceFrames(dev.upload_frames(audio), audio.shape[0])
+                frames = dev.track_frames(audio, rate, internal)
                 if role == "target":
-                    peaks = dev.peak_count(frames, 2 * audio.shape[0])
+                    peaks = dev.peak_count(frames, 2 * frames.frames)
+        # (the host array is not the final track when the device has changed its rate or its channels)
+        changed = frames is not None and (rate != internal or pcm_channels(audio) != 2)
         try:
-            tracks.append(check(audio, rate, config, role, peaks=peaks))
+            tracks.append(check(audio, rate, config, role, peaks=peaks, on_device=changed))
         except Exception:
             for f in resident + [frames]:
                 if f is not None:
                     f.release()
             raise
         resident.append(frames)
+        converted.append(frames if changed else None)
     (target, target_rate), (reference, reference_rate) = tracks
     try:
         if not config.allow_equality:
-            check_equality(target, reference)
+            check_equality(target, reference, converted)
+        lengths = [array.shape[0] if frames is None else frames.frames
+                   for array, frames in zip((target, reference), converted)]
+        channels = [pcm_channels(array) if frames is None else 2 for array, frames in zip((target, reference), converted)]
         consistent = (
-            target_rate == reference_rate == config.internal_sample_rate
-            and pcm_channels(target) == pcm_channels(reference) == 2
-            and min(target.shape[0], reference.shape[0]) > config.fft_size
+            target_rate == reference_rate == internal
+            and channels[0] == channels[1] == 2
+            and min(lengths) > config.fft_size
         )
         if not consistent:
             raise ModuleError(Code.ERROR_VALIDATION)

@@ -24,6 +24,8 @@ static inline int roctxRangePop() { return 0; }
 #include "fir_plan.h"
 #include "host_params.h"
 #include "mgx_kernels.h"
+#include "resample_kernel.h"
+#include "resample_plan.h"
 
 using namespace mgx;
 
@@ -224,6 +226,14 @@ struct mgx_handle {
     DevBuf lim_tables;                      // general filter orders: matrix powers and look-back matrices
     std::vector<double> lim_tables_host;
     DevBuf fir_scratch;
+    // mgx_resample: the weights of every rate pair this handle has converted, designed and uploaded once
+    struct ResampleDev {
+        std::shared_ptr<const ResamplePlan> plan;
+        std::vector<double> host;           // the matrix as uploaded (resample_device_matrix)
+        DevBuf matrix;
+    };
+    std::map<std::pair<int, int>, ResampleDev> resample_plans;
+    long long resample_designs = 0;         // plans designed and uploaded so far (mgx_resample_plan)
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // set by a kernel whose bounded wait expired (limiter look-back, level-correction round): one word of
@@ -1159,7 +1169,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
 // ---------------------------------------------------------------------------
 extern "C" {
 
-int mgx_version(void) { return 100; }
+int mgx_version(void) { return 101; }
 const char* mgx_last_error(void) { return g_error.c_str(); }
 
 int mgx_device_count(int* count) {
@@ -1593,6 +1603,68 @@ int mgx_pcm_encode(mgx_handle* h, const float* x_dev, int64_t samples, int32_t b
     const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 8192);
     hipLaunchKernelGGL(k_pcm_encode, dim3(grid), dim3(256), 0, h->stream, x_dev, (long long)samples, bits, pcm_dev);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels, int32_t rate_in, int32_t rate_out,
+                 float* out_dev, int64_t out_capacity_frames, int64_t* n_out) {
+    // everything that depends on the numbers alone is settled before the handle is touched
+    if (!n_out) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (channels != 1 && channels != 2) return fail(MGX_ERR_ARGUMENT, "a track to convert has one or two channels");
+    if (rate_in <= 0 || rate_out <= 0) return fail(MGX_ERR_ARGUMENT, "sample rates must be positive");
+    if (rate_in == rate_out) return fail(MGX_ERR_ARGUMENT, "the track is at the requested rate already");
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
+    ResampleGeometry g;
+    std::string why;
+    if (resample_geometry(rate_in, rate_out, &g, &why) != 0)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_resample " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " Hz: " + why);
+    const int64_t frames = resample_length(n, rate_in, rate_out);
+    if (n > RESAMPLE_FRAMES_MAX || frames > RESAMPLE_FRAMES_MAX)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_resample: tracks of more than 500 million frames are not converted here");
+    *n_out = frames;
+    if (!out_dev) return 0;                                     // the caller asked for the length only
+    if (!h || !x_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (out_capacity_frames < frames) return fail(MGX_ERR_ARGUMENT, "the output holds fewer frames than the conversion gives");
+    if (frames == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    mgx_handle::ResampleDev& dev = h->resample_plans[{rate_in, rate_out}];
+    if (!dev.matrix.p) {
+        dev.plan = resample_design(rate_in, rate_out);
+        if (!dev.plan) return fail(MGX_ERR_UNSUPPORTED, "mgx_resample: no plan for these rates");
+        dev.host = resample_device_matrix(*dev.plan);
+        MGX_TRY(ensure(h, dev.matrix, dev.host.size() * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(dev.matrix.p, dev.host.data(), dev.host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        ++h->resample_designs;
+    }
+    ResampleArgs a;
+    a.x = x_dev;
+    a.n = n;
+    a.w = (const double*)dev.matrix.p;
+    a.L = g.L;
+    a.M = g.M;
+    a.W = g.W;
+    a.out = out_dev;
+    a.n_out = frames;
+    const unsigned grid = (unsigned)((frames + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK);
+    const size_t lds = (size_t)g.span * channels * sizeof(float);
+    if (channels == 2)
+        hipLaunchKernelGGL(k_resample<2>, dim3(grid), dim3(RESAMPLE_BLOCK), lds, h->stream, a);
+    else
+        hipLaunchKernelGGL(k_resample<1>, dim3(grid), dim3(RESAMPLE_BLOCK), lds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mgx_resample_plan(mgx_handle* h, int32_t rate_in, int32_t rate_out, void** weights_dev, int32_t* phases,
+                      int32_t* row_entries, int64_t* designed) {
+    if (!h || !weights_dev || !phases || !row_entries || !designed) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const auto it = h->resample_plans.find({rate_in, rate_out});
+    if (it == h->resample_plans.end() || !it->second.matrix.p)
+        return fail(MGX_ERR_ARGUMENT, "no track has been converted between these rates on this handle yet");
+    *weights_dev = it->second.matrix.p;
+    *phases = it->second.plan->g.L;
+    *row_entries = it->second.plan->g.W;
+    *designed = h->resample_designs;
     return 0;
 }
 

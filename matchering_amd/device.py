@@ -13,7 +13,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _native
-from ._native import MgxReport, check, library
+from ._native import MgxError, MgxReport, check, library
+from .audio_io import pcm_channels
 
 
 class _PinnedPool:
@@ -143,6 +144,58 @@ class DeviceFrames:
 
     def release(self):
         self.buf.release()
+
+    def host(self):
+        """The frames as a float32 (frames, 2) array (pinned): ``checker.check_equality`` of a converted track."""
+        dev = self.buf.device
+        with dev.lock:
+            return dev.download(self.buf, (self.frames, 2))
+
+
+def converted_length(frames, channels, rate_in, rate_out):
+    """Frames ``mgx_resample`` makes of a track, ``int(frames * (rate_out / rate_in))``, or None when the library
+    leaves this conversion to the host (``MGX_ERR_UNSUPPORTED``: more than 4096 phases, ...).  Needs no GPU."""
+    from .log import debug
+
+    n_out = ctypes.c_int64()
+    rc = library().mgx_resample(None, None, int(frames), int(channels), int(rate_in), int(rate_out), None, 0,
+                                ctypes.byref(n_out))
+    if rc == _native.ERR_UNSUPPORTED:
+        debug(f"{rate_in} Hz -> {rate_out} Hz is converted on the host: "
+              + library().mgx_last_error().decode("utf-8", "replace"))
+        return None
+    check(rc)
+    return n_out.value
+
+
+def takes_resident(audio, rate, internal_rate):
+    """Whether a loaded track goes to the GPU as its file holds it, to become (frames, 2) float32 at the internal
+    rate there (``Device.track_frames``): one or two channels of samples float32 holds exactly -- int16, packed
+    24-bit, float32 -- at a rate ``mgx_resample`` converts; at the internal rate itself also 32-bit integers, which
+    ``mgx_pcm_decode`` rounds as the host would.  An off-rate file of 32-bit integers or float64 keeps the host's
+    float64 resampler, which sees every bit of it."""
+    channels = pcm_channels(audio)
+    if channels not in (1, 2) or audio.shape[0] == 0:
+        return False
+    if rate == internal_rate:
+        return audio.dtype.kind in "iu" or audio.dtype == np.float32
+    if audio.dtype not in (np.int16, np.uint8, np.float32):
+        return False
+    return converted_length(audio.shape[0], channels, rate, internal_rate) is not None
+
+
+def final_frames(audio, rate, internal_rate):
+    """Frame count of the track ``Device.track_frames`` makes of ``audio``."""
+    if rate == internal_rate:
+        return audio.shape[0]
+    return converted_length(audio.shape[0], pcm_channels(audio), rate, internal_rate)
+
+
+def _both_columns(audio):
+    """A mono track in its file's encoding -> the same samples in two columns (dsp.py:45-46)."""
+    if audio.dtype == np.uint8:                                   # packed 24-bit: (n, 3) -> (n, 6)
+        return np.ascontiguousarray(np.repeat(audio.reshape(-1, 1, 3), 2, axis=1).reshape(-1, 6))
+    return np.repeat(audio, repeats=2, axis=1)
 
 
 class DeviceBuffer:
@@ -291,6 +344,46 @@ class Device:
         check(library().mgx_pcm_decode(self.handle, ctypes.c_void_p(raw.ptr), samples, bits, ctypes.c_void_p(out.ptr)))
         raw.release()           # (recycled by later work on this stream only, which is ordered behind the decode)
         return out
+
+    def resample_frames(self, buf, frames, channels, rate_in, rate_out):
+        """checker.py:30-45 on float32 frames in HBM (``mgx_resample``): (frames, channels) at ``rate_in`` -> a new
+        ``DeviceFrames`` of (n_out, 2) at ``rate_out``, queued on this device's stream.  Raises ``MgxError`` with
+        ``code == ERR_UNSUPPORTED`` for the ratios the library leaves to the host."""
+        lib = library()
+        n_out = ctypes.c_int64()
+        check(lib.mgx_resample(None, None, int(frames), int(channels), int(rate_in), int(rate_out), None, 0,
+                               ctypes.byref(n_out)))
+        out = DeviceBuffer(self, max(n_out.value * 8, 1))
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        try:
+            check(lib.mgx_resample(self.handle, ctypes.c_void_p(ptr), int(frames), int(channels), int(rate_in),
+                                   int(rate_out), ctypes.c_void_p(out.ptr), n_out.value, ctypes.byref(n_out)))
+        except Exception:
+            out.release()
+            raise
+        return DeviceFrames(out, n_out.value)
+
+    def resample_plan(self, rate_in, rate_out):
+        """(device address of the weights, phases, entries per phase, plans designed on this handle so far) for a
+        rate pair this handle has converted (``mgx_resample_plan``)."""
+        ptr, phases, width, designed = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        check(library().mgx_resample_plan(self.handle, int(rate_in), int(rate_out), ctypes.byref(ptr),
+                                          ctypes.byref(phases), ctypes.byref(width), ctypes.byref(designed)))
+        return ptr.value, phases.value, width.value, designed.value
+
+    def track_frames(self, audio, rate, internal_rate):
+        """A loaded track (``takes_resident``) -> ``DeviceFrames`` at the internal rate: uploaded as the file holds it,
+        decoded (``mgx_pcm_decode``) and, off-rate, converted (``mgx_resample``, which also gives a mono track its
+        second column).  A mono track at the internal rate is given its second column on the way up."""
+        if rate == internal_rate:
+            if pcm_channels(audio) == 1:
+                audio = _both_columns(audio)
+            return DeviceFrames(self.upload_frames(audio), audio.shape[0])
+        decoded = self.upload_frames(audio)
+        try:
+            return self.resample_frames(decoded, audio.shape[0], pcm_channels(audio), rate, internal_rate)
+        finally:
+            decoded.release()         # (recycled by later work on this stream only, which is ordered behind the kernel)
 
     def peak_count(self, buf, samples):
         """dsp.py:49-54 count_max_peaks of float32 samples in HBM: (largest magnitude, samples on it)."""

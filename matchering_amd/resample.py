@@ -13,7 +13,10 @@ to the audible, not to the numerical.  Parity with the package itself is unpinne
 tests/test_resample.py holds this file against a literal restatement of the package's loops
 (oracle/resampy_oracle.py) and against what a band-limited resampler does to a sine.
 
-Host code: this is the loader's path for off-rate files, not the timed path.
+Host code.  With a GPU the loaders convert off-rate files there (``mgx_resample``: the same sum, phase by phase, in
+float64 -- csrc/resample_plan.cpp restates ``_Plan`` and ``_prototype``); this module is the fallback (no GPU, 32-bit
+integer and float64 files, ratios the library refuses) and the reference the device is tested against (DESIGN.md
+section 6).
 """
 import numpy as np
 
