@@ -202,6 +202,7 @@ inline Iir1f to_f32(const Iir1& f) {
     Iir1f r;
     r.b0 = (float)f.b0;
     r.alpha = (float)f.alpha;
+    r.gamma = (float)(f.alpha - 1.0);
     r.beta = (float)f.beta;
     return r;
 }

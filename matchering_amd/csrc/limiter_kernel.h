@@ -74,7 +74,14 @@ struct Iir1 {
 };
 struct Iir1f {
     float b0, alpha, beta;
+    float gamma;                   // alpha - 1, rounded on its own: see iir1_step()
 };
+
+// z' = alpha z + beta x on a state that is not small (an envelope near 0.7 entering a block): alpha sits within 1e-3 of 1,
+// where float32 is 6e-8 apart, so alpha rounded to float32 is off by up to 3e-8 and sixteen steps of `alpha z` drift by up
+// to 16 x 3e-8 x z, always the same way.  z + (gamma z + beta x) with gamma = alpha - 1 rounded on its own (relative 6e-8 of a
+// small number) has no such drift.
+MGX_HD float iir1_step(const Iir1f& f, float z, float x) { return z + fmaf(f.gamma, z, f.beta * x); }
 
 struct LimiterArgs {
     const float2* y;               // (n,2) level-corrected result before the final gains
@@ -203,7 +210,9 @@ struct LimiterBlock {
         Geometry g;
         g.gw = (hw + E - 1) / E;
         const int hab = (ha + E - 1) / E;
-        g.gl = (hw + hb + E - 1) / E;          // left: only the sh window (the attack state is carried in)
+        // left: the sh window (the attack state is carried in), and not less than the six frames in front of the core, with
+        // their sl windows, that the right filtfilt edge reads when the track ends inside the core's first block
+        g.gl = (hw + (hb > 6 ? hb : 6) + E - 1) / E;
         g.gr = hab + g.gw;                      // right: backward warm-up + sl window
         g.core_blocks = T - g.gl - g.gr;
         g.chunk = g.core_blocks * E;
@@ -381,14 +390,14 @@ struct LimiterBlock {
         float s = z0;
         MGX_UNROLL
         for (int j = 0; j < E; ++j)
-            if (j < count) s = fmaf(f.alpha, s, f.beta * x[j]);
+            if (j < count) s = iir1_step(f, s, x[j]);
         return s;
     }
     static MGX_HD float run_backward(const Iir1f& f, const float (&x)[E], int count, float z0) {
         float s = z0;
         MGX_UNROLL
         for (int j = E - 1; j >= 0; --j)
-            if (j < count) s = fmaf(f.alpha, s, f.beta * x[j]);
+            if (j < count) s = iir1_step(f, s, x[j]);
         return s;
     }
     // outputs y[j] = b0 x[j] + z[j-1] with the true state z0 entering the block; returns the state
@@ -400,7 +409,7 @@ struct LimiterBlock {
         for (int j = 0; j < E; ++j) {
             if (j < count) {
                 y[j] = fmaf(f.b0, x[j], s);
-                s = fmaf(f.alpha, s, f.beta * x[j]);
+                s = iir1_step(f, s, x[j]);
             } else {
                 y[j] = 0.f;
             }
@@ -413,7 +422,7 @@ struct LimiterBlock {
         for (int j = E - 1; j >= 0; --j) {
             if (j < count) {
                 y[j] = fmaf(f.b0, x[j], s);
-                s = fmaf(f.alpha, s, f.beta * x[j]);
+                s = iir1_step(f, s, x[j]);
             } else {
                 y[j] = 0.f;
             }
@@ -533,6 +542,18 @@ struct LimiterBlock {
                 }
                 th.inject_left = th.base == 0;
                 th.inject_right = valid > 0 && th.base + valid == a.n;
+                // filtfilt_right_state reads sl of the track's last seven frames.  In a last chunk whose core holds fewer
+                // than seven, those in front of it lie in the left halo, whose threads form no sl, and the workgroup's
+                // LDS is undefined there: the first core thread forms them itself, frame by frame from the g0 plane (the
+                // left halo holds them and their windows: geometry()).
+                if (th.inject_right && tid == a.gl && valid < 7) {
+                    const float* row = plane(lds) + tid * STRIDE;
+                    for (int d = valid - 7; d < 0; ++d) {
+                        float m = 0.f;
+                        for (int e = d - a.hw; e <= d + a.hw; ++e) m = pmax(m, row[rel(e)]);
+                        edge_sl(lds)[14 + d - valid] = m;
+                    }
+                }
             }
             if (valid > 0) {
                 const double decay = block_decay(a.pa16, a.att.alpha, valid);
@@ -670,7 +691,7 @@ struct LimiterBlock {
         for (int j = 0; j < E; ++j) {
             const bool in = j < valid;
             const float ho = in ? fmaf(a.holdf.b0, th.sh[j], z) : 0.f;
-            if (in) z = fmaf(a.holdf.alpha, z, a.holdf.beta * th.sh[j]);
+            if (in) z = iir1_step(a.holdf, z, th.sh[j]);
             const float ga = in ? th.yb[j] + pw : 0.f;
             pw *= a.attf.alpha;
             th.x2[j] = fmaxf(th.sh[j], ho);                      // hyrax.py:73
@@ -692,7 +713,7 @@ struct LimiterBlock {
         for (int j = 0; j < E; ++j) {
             const bool in = j < valid;
             const float ro = in ? fmaf(a.relf.b0, th.x2[j], z) : 0.f;
-            if (in) z = fmaf(a.relf.alpha, z, a.relf.beta * th.x2[j]);
+            if (in) z = iir1_step(a.relf, z, th.x2[j]);
             gn[j] = 1.0f - fmaxf(th.mx[j], ro);                  // hyrax.py:75,97 without g0 (phase_store)
         }
     }

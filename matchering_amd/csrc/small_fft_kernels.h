@@ -40,16 +40,16 @@ __global__ __launch_bounds__(256) void k_analyze_small(AnalysisArgs a0, Analysis
     for (int s = s0 + tid; s < s1; s += 256) {
         const float2* x = a.x + (long long)d * a.piece + (long long)s * F;
         float2 v[F];
-        float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < F; ++j) {
             const float2 lr = x[j];
             const float m = (lr.x + lr.y) * 0.5f;                // dsp.py:59-60
             v[j] = make_float2(m, m - lr.y);                     // dsp.py:62
-            ss = fmaf(m, m, ss);
+            // (in float64, where a float32 square is exact: a float32 chain over the segment's 16 or 32 frames rounds the
+            // same way in every segment of periodic material, and a piece's RMS was then off by up to 1.4e-7 of itself)
+            sumsq = fma((double)m, (double)m, sumsq);
             peak = fmaxf(peak, fmaxf(fabsf(lr.x), fabsf(lr.y)));
         }
-        sumsq += (double)ss;
         dft_regs<F, false>(v);                                   // X[q] sits at v[bitrev(q)]
 #pragma unroll
         for (int k = 0; k <= HALF; ++k) {

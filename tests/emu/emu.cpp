@@ -7,6 +7,7 @@
 // test-suite uses it to check the index arithmetic of the kernels against the
 // oracle without a GPU.  It is not part of the product and is never loaded by
 // matchering_amd.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -362,11 +363,22 @@ static int analyze_impl(const float* x, long long n, const mgx_config* cfg, int 
         FOR_THREADS(F::T) AB::init(th[tid]);
         int s0, s1;
         Analysis2Block<LOG2N>::chunk_segments(a, ch, s0, s1);
+        // k_analyze<14> asks for the next segment's frames behind the row pass, unconditionally: behind the last segment of
+        // a chunk the request runs into the next chunk's frames or past the track, where the view's range check answers
+        // zeros, and is dropped.  The same sequence here, so that the request itself goes through the host's range check.
+        constexpr bool AHEAD = LOG2N == 14;
+        std::vector<typename AB::Raw> ahead(AHEAD ? F::T : 0);
+        if (AHEAD) { FOR_THREADS(F::T) AB::fetch(tid, d * piece + (long long)s0 * F::N, a, ahead[tid]); }
         for (int s = s0; s < s1; ++s) {
             const long long start = d * piece + (long long)s * F::N;
-            FOR_THREADS(F::T) { typename AB::Raw raw; AB::fetch(tid, start, a, raw); AB::phase_load(tid, raw, ps[tid], th[tid], lds.data()); }
+            if (AHEAD) {
+                FOR_THREADS(F::T) AB::phase_load(tid, ahead[tid], ps[tid], th[tid], lds.data());
+            } else {
+                FOR_THREADS(F::T) { typename AB::Raw raw; AB::fetch(tid, start, a, raw); AB::phase_load(tid, raw, ps[tid], th[tid], lds.data()); }
+            }
             local_phases<F>(mid_phases<F>(false, lds.data(), mid_table.data()) +
                             std::vector<Phase>{[&](int tid) { AB::phase_row(tid, own[tid], lds.data()); }});
+            if (AHEAD) { FOR_THREADS(F::T) AB::fetch(tid, start + F::N, a, ahead[tid]); }
             FOR_THREADS(F::T) AB::phase_magnitudes(tid, own[tid], th[tid], lds.data());
         }
         if (ch == a.chunks_per_piece - 1) {
@@ -676,6 +688,9 @@ static int limit_impl(const LimiterParams& lp, const float* x, long long n, cons
         return s;
     };
     for (long long chunk = 0; chunk < a.nchunks; ++chunk) {
+        // a workgroup's LDS starts out undefined: whatever a chunk reads it must have written itself, not inherited from
+        // the chunk this loop ran before it
+        std::fill(lds.begin(), lds.end(), 1.0e6f);           // (not a NaN: fmaxf would drop it)
         FOR_THREADS(LB::T) {
             float pm[LB::E / 2];
             LB::phase_load(tid, chunk, a, lds.data(), pm);
@@ -784,6 +799,9 @@ static int limit_general_impl(const LimiterParams& lp, const float* x, long long
         FOR_THREADS(LB::T) LG::scan_top(lds.data(), tid);
     };
     for (long long chunk = 0; chunk < a.nchunks; ++chunk) {
+        // a workgroup's LDS starts out undefined: whatever a chunk reads it must have written itself, not inherited from
+        // the chunk this loop ran before it
+        std::fill(lds.begin(), lds.end(), 1.0e6f);           // (not a NaN: fmaxf would drop it)
         FOR_THREADS(LB::T) {
             float pm[LB::E / 2];
             LB::phase_load(tid, chunk, a, lds.data(), pm);
@@ -958,4 +976,20 @@ extern "C" int emu_limiter_quiet_ok(const mgx_config* cfg) {
     LimiterArgs a;
     limiter_fill(lp, (float)cfg->threshold, a);
     return a.quiet_ok;
+}
+
+// What limiter_params (host_params.h) decides for a configuration: blocks per chunk the kernel runs with (256 or 1024),
+// the blocks and frames of a chunk's core, the halos in blocks, and which kernel takes it (0: k_limit, 2 / 3:
+// k_limit_general<K>).  Tests derive chunk edges from this, not from a number of their own.  < 0: parameters refused.
+extern "C" int emu_limiter_geometry(const mgx_config* cfg, int* threads, int* core_blocks, int* chunk, int* gl, int* gr,
+                                    int* general) {
+    LimiterParams lp;
+    if (!limiter_params(*cfg, lp).empty()) return -1;
+    if (threads) *threads = lp.threads;
+    if (core_blocks) *core_blocks = lp.geo.core_blocks;
+    if (chunk) *chunk = lp.geo.chunk;
+    if (gl) *gl = lp.geo.gl;
+    if (gr) *gr = lp.geo.gr;
+    if (general) *general = lp.general;
+    return 0;
 }
