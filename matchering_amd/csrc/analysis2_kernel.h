@@ -534,7 +534,7 @@ struct AnalysisQuad {
 
 // ---------------------------------------------------------------------------
 // Scalar epilogue of the analysis (host restatement used by the CPU emulation; the device
-// version is k_levels in mgx_kernels.h).  match_levels.py:62-71,93-103.
+// version is k_levels in levels_kernels.h).  match_levels.py:62-71,93-103.
 // ---------------------------------------------------------------------------
 struct TrackStats {
     double peak;             // max |x| over the whole track (dsp.py:97)

@@ -204,7 +204,7 @@ struct Fft2 {
     // (the middle passes and the row pass, in both directions) deals its butterflies to the waves in the same
     // contiguous runs.  A wave then reads only what it wrote itself between pass 0 and the inverse of pass 0,
     // so the passes in between need no workgroup barrier, only program order within the wave (pass_sync()
-    // in mgx_kernels.h): one barrier per transform and direction instead of one per pass.
+    // in wave_util.h): one barrier per transform and direction instead of one per pass.
     static constexpr int W = T / 64;
     static constexpr bool WAVE_LOCAL = P >= 3 && R0 % W == 0;
     template <int PASS>

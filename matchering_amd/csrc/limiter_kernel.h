@@ -41,7 +41,7 @@
 //    the attack pole, a handful for the 7 Hz hold filter, ~170 for the 0.27 Hz release filter).
 //    No chunk ever waits for another chunk's look-back of the same filter, so the dependency
 //    depth is two (release aggregates need the exact hold output) however long the track is.
-//    A chunk is its workgroup's number (k_limit in mgx_kernels.h: the dispatcher hands workgroups out in
+//    A chunk is its workgroup's number (k_limit in limiter_kernels.h: the dispatcher hands workgroups out in
 //    the order of their numbers, so every chunk a workgroup waits for has already started -- an
 //    assumption about ONE launch that is alone on the chip, observed on this firmware and partition
 //    mode, documented nowhere) or, on a handle that has ever seen a wait expire and under

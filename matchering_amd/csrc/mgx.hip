@@ -20,6 +20,7 @@ static inline int roctxRangePop() { return 0; }
 #include <vector>
 
 #include "../../include/mgx.h"
+#include "code_sizes.h"
 #include "fir_design.h"
 #include "fir_plan.h"
 #include "host_params.h"
@@ -57,97 +58,6 @@ static int fail(int code, const std::string& msg) {
     } while (0)
 
 // ---------------------------------------------------------------------------
-// code sizes of the big kernels, from this library's own device code object (mgx_kernels.h, "code warming")
-// ---------------------------------------------------------------------------
-// libmgx.so -> section .hip_fatbin -> clang offload bundle -> the gfx950 ELF -> .symtab.  Anything unexpected
-// (a compressed bundle, a stripped table) leaves the sizes at zero and the kernels do not warm.
-#include <dlfcn.h>
-#include <elf.h>
-
-#include <fstream>
-#include <iterator>
-
-static const char* const CODE_NAMES[CODE_KERNELS] = {"k_analyzeILi", "k_match_curve", "k_conv_prepILi", "k_convILi",
-                                                     "k_correction_round", "k_correction_tail", "k_limitILi"};
-static bool elf_ok(const std::vector<char>& f, size_t at) {
-    return at + sizeof(Elf64_Ehdr) <= f.size() && std::memcmp(f.data() + at, ELFMAG, SELFMAG) == 0 &&
-           f[at + EI_CLASS] == ELFCLASS64;
-}
-// bytes[family][variant]: variant = the first template argument (log2 of the transform; 256 / 1024 blocks of the
-// limiter -> 0 / 1), 0 for plain kernels; the smaller size where two instantiations share a variant
-static void code_sizes_from_library(int (&bytes)[CODE_KERNELS][CODE_VARIANTS]) {
-    for (auto& row : bytes)
-        for (int& b : row) b = 0;
-    Dl_info info;
-    if (!dladdr(reinterpret_cast<const void*>(&code_sizes_from_library), &info) || !info.dli_fname) return;
-    std::ifstream in(info.dli_fname, std::ios::binary);
-    if (!in) return;
-    const std::vector<char> f((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-    if (!elf_ok(f, 0)) return;
-    const Elf64_Ehdr* eh = reinterpret_cast<const Elf64_Ehdr*>(f.data());
-    if (eh->e_shoff + (size_t)eh->e_shnum * sizeof(Elf64_Shdr) > f.size() || eh->e_shstrndx >= eh->e_shnum) return;
-    const Elf64_Shdr* sh = reinterpret_cast<const Elf64_Shdr*>(f.data() + eh->e_shoff);
-    const char* names = f.data() + sh[eh->e_shstrndx].sh_offset;
-    size_t fat = 0, fat_size = 0;
-    for (int i = 0; i < eh->e_shnum; ++i)
-        if (std::strcmp(names + sh[i].sh_name, ".hip_fatbin") == 0) { fat = sh[i].sh_offset; fat_size = sh[i].sh_size; }
-    static const char MAGIC[] = "__CLANG_OFFLOAD_BUNDLE__";
-    if (!fat || fat + fat_size > f.size() || fat_size < 32 || std::memcmp(f.data() + fat, MAGIC, 24) != 0) return;
-    uint64_t entries = 0;
-    std::memcpy(&entries, f.data() + fat + 24, 8);
-    size_t pos = fat + 32, dev = 0;
-    for (uint64_t e = 0; e < entries && pos + 24 <= fat + fat_size; ++e) {
-        uint64_t off = 0, size = 0, tsize = 0;
-        std::memcpy(&off, f.data() + pos, 8);
-        std::memcpy(&size, f.data() + pos + 8, 8);
-        std::memcpy(&tsize, f.data() + pos + 16, 8);
-        if (pos + 24 + tsize > fat + fat_size) return;
-        const std::string triple(f.data() + pos + 24, f.data() + pos + 24 + tsize);
-        if (triple.find("gfx950") != std::string::npos && fat + off + size <= f.size()) dev = fat + off;
-        pos += 24 + tsize;
-    }
-    if (!dev || !elf_ok(f, dev)) return;
-    const Elf64_Ehdr* de = reinterpret_cast<const Elf64_Ehdr*>(f.data() + dev);
-    if (dev + de->e_shoff + (size_t)de->e_shnum * sizeof(Elf64_Shdr) > f.size()) return;
-    const Elf64_Shdr* ds = reinterpret_cast<const Elf64_Shdr*>(f.data() + dev + de->e_shoff);
-    for (int i = 0; i < de->e_shnum; ++i) {
-        if (ds[i].sh_type != SHT_SYMTAB || ds[i].sh_link >= de->e_shnum) continue;
-        const char* str = f.data() + dev + ds[ds[i].sh_link].sh_offset;
-        const size_t count = ds[i].sh_size / sizeof(Elf64_Sym);
-        const Elf64_Sym* sym = reinterpret_cast<const Elf64_Sym*>(f.data() + dev + ds[i].sh_offset);
-        for (size_t k = 0; k < count; ++k) {
-            if (ELF64_ST_TYPE(sym[k].st_info) != STT_FUNC || sym[k].st_size == 0) continue;
-            const char* name = str + sym[k].st_name;
-            if (std::strstr(name, "k_conv_delayILi")) {              // the delay-line convolution: CODE_CONV's last variant
-                bytes[CODE_CONV][CODE_VARIANT_CONV_DELAY] = (int)sym[k].st_size;
-                continue;
-            }
-            if (std::strstr(name, "k_conv_wide_prepILi")) {          // ... and its filter preparation
-                bytes[CODE_CONV_PREP][CODE_VARIANT_CONV_WIDE] = (int)sym[k].st_size;
-                continue;
-            }
-            if (std::strstr(name, "k_conv_wideILi")) {               // N = 4F: the slot no k_conv<L> uses
-                bytes[CODE_CONV][CODE_VARIANT_CONV_WIDE] = (int)sym[k].st_size;
-                continue;
-            }
-            for (int c = 0; c < CODE_KERNELS; ++c) {
-                const char* hit = std::strstr(name, CODE_NAMES[c]);
-                if (!hit) continue;
-                int variant = 0;
-                const size_t len = std::strlen(CODE_NAMES[c]);
-                if (len >= 3 && std::strcmp(CODE_NAMES[c] + len - 3, "ILi") == 0) {      // templated: ...ILi<number>E
-                    const int number = std::atoi(hit + len);
-                    variant = number == 256 ? 0 : number == 1024 ? 1 : number;
-                }
-                if (variant < 0 || variant >= CODE_VARIANTS) continue;
-                int& slot = bytes[c][variant];
-                if (slot == 0 || (int)sym[k].st_size < slot) slot = (int)sym[k].st_size;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // handle
 // ---------------------------------------------------------------------------
 // a device allocation that frees itself (the handle's buffers, and the temporaries of the FIR operator builds on every
@@ -175,7 +85,7 @@ struct PlanDev {
     void* blob = nullptr;       // FirPlanHost tables
     double* M = nullptr;        // [bins][bins] raw -> smooth operator
     int2* band = nullptr;       // [bins] columns [x, y) of each row that matter (k_fir_band)
-    // the same operator in two packed, banded factors (fft_size >= 16384; mgx_kernels.h, k_fir_apply_a / _b)
+    // the same operator in two packed, banded factors (fft_size >= 16384; fir_kernels.h, k_fir_apply_a / _b)
     struct Factor {
         double* packed = nullptr;       // the rows' windows, one after the other
         FactorRow* rows = nullptr;      // [rows] window of each row and where it starts in `packed`
@@ -258,7 +168,7 @@ struct mgx_handle {
     bool avoid_tail = false;                // sticky after such a report: rounds 1..K-1 as one launch each (MGX_NO_TAIL=1: always)
     bool requeued = false;                  // the last check_device_error queued the call again
     // the limiter's chunks are its workgroups' numbers; after a look-back wait has expired once on this handle they are
-    // drawn from an atomic ticket instead, which does not lean on the dispatch order (k_limit, mgx_kernels.h)
+    // drawn from an atomic ticket instead, which does not lean on the dispatch order (k_limit, limiter_kernels.h)
     bool limiter_tickets = false;
     hipEvent_t lim_done = nullptr;                                // behind this handle's latest limiter launch (LimiterChain)
     int masters_outstanding = 0;            // mgx_master calls queued since the last check of the error words
@@ -329,6 +239,12 @@ struct StageScope {
 // control words shared by the kernels that count arrivals: [0] limiter ticket, [1] limiter error flag,
 // [4] correction-round arrivals.  Zeroed when allocated; every user leaves its word at zero.
 static int ensure_ctrl(mgx_handle* h);
+// one stages.main: every launch queued on the handle's stream (check_device_error may queue the last call again), and
+// the boundary around it
+static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c);
+static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
+                       int64_t n_reference, const mgx_config* cfg, const float* fir_given, float* result_dev,
+                       float* result_no_limiter_dev, float* result_no_limiter_normalized_dev, mgx_report* report);
 
 static int get_twiddles(mgx_handle* h, int log2n, const float2** out) {
     auto it = h->twiddles.find(log2n);
@@ -564,7 +480,7 @@ static int run_levels(mgx_handle* h, const mgx_config* cfg, TrackWork* first, Tr
 
 // device-side FIR design (fir_plan.h): spectra partial sums of both tracks -> h->taps ([2][F] float),
 // level gain c0 -> h->scalars[0].  No host synchronisation.  The chain raw -> smooth is one dense
-// operator per plan (mgx_kernels.h), built on first use.
+// operator per plan (fir_kernels.h), built on first use.
 static int build_fir_operator(mgx_handle* h, const FirPlanView& pl, double** out, int2** band_out) {
     const size_t per = (size_t)3 * pl.bins + (size_t)3 * pl.nlog + pl.lw.anchors;
     const int batch = std::min(pl.bins, 256);
@@ -622,7 +538,7 @@ static int pack_fir_factor(mgx_handle* h, double* dense, int rows, int cols, Pla
     return 0;
 }
 
-// raw -> smooth as B * (A * raw) through the anchors' LOWESS fits (mgx_kernels.h): unit vectors pushed through the two
+// raw -> smooth as B * (A * raw) through the anchors' LOWESS fits (fir_kernels.h): unit vectors pushed through the two
 // halves of the chain, 256 at a time, gathered into dense matrices that live only until their windows are packed
 static int build_fir_factors(mgx_handle* h, const FirPlanView& pl, PlanDev& pd) {
     const size_t per = (size_t)3 * pl.bins + (size_t)3 * pl.nlog + pl.lw.anchors;
@@ -969,6 +885,102 @@ static int limiter_state(mgx_handle* h, long long n, const LimiterParams& lp, un
     return 0;
 }
 
+static const char* const TOO_MANY_PIECES = "too many analysis pieces for the level-correction kernel's LDS";
+
+// Stage 3 (stages.py:138-170), every round queued on the handle's stream: one launch per round, the last round also
+// derives the peak / early-out / normalisation scalars.  `nblocks`: the per-pair peaks the convolution left in
+// h->block_peak.  `lp`: the limiter's parameters when a limited result follows, else null; round 0's grid then presets
+// the limiter's look-back words (`*limiter_preset`).
+static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const TrackWork& rw,
+                          long long n_target, long long nblocks, const LimiterParams* lp, bool* limiter_preset) {
+    CorrectionState* cs = (CorrectionState*)h->cstate.p;
+    RoundArgs ra;
+    ra.mid = (const float*)h->mid.p;
+    ra.piece = tw.piece;
+    ra.divisions = tw.divisions;
+    ra.chunks = std::max(1, 1024 / tw.divisions);     // ~1000 workgroups: each pays one publish + ticket
+    // (round 0's partial sums, and behind them the peak words of k_correction_tail's workgroups)
+    MGX_TRY(ensure(h, h->partial, (size_t)2 * ra.divisions * ra.chunks * sizeof(double)));
+    ra.partial = (double*)h->partial.p;
+    // arrival counters [1 + divisions], zero between launches; the 16 gain words of k_correction_tail
+    // live in their own buffer (a layout that moved with `divisions` would leave one call's preset
+    // gain words where the next call counts arrivals)
+    const size_t ctr_bytes = (size_t)(1 + ra.divisions) * sizeof(unsigned);
+    // at most ~128 workgroups in k_correction_tail, at most 64 chunks (the lanes of a wave) per workgroup
+    const int tail_groups = std::max((ra.chunks + 63) / 64, std::max(1, std::min(ra.chunks, 128 / ra.divisions)));
+    const bool use_tail = cfg->rms_correction_steps > 1 && !h->avoid_tail;
+    const int tail_total = use_tail ? ra.divisions * tail_groups : 0;
+    const int tail_rounds = use_tail ? cfg->rms_correction_steps - 1 : 0;
+    MGX_TRY(ensure(h, h->tail_gains, ((size_t)tail_rounds + 1 + (size_t)tail_rounds * tail_total) * sizeof(unsigned long long)));
+    ra.tail_total = tail_total;
+    ra.tail_rounds = tail_rounds;
+    if (h->round_ctr.bytes < ctr_bytes) {                 // zeroed when (re)allocated, reset by each launch
+        MGX_TRY(ensure(h, h->round_ctr, std::max(ctr_bytes, (size_t)4096)));
+        HIP_TRY(hipMemsetAsync(h->round_ctr.p, 0, h->round_ctr.bytes, h->stream));
+    }
+    ra.arrivals = (unsigned*)h->round_ctr.p;
+    const size_t wgs = (size_t)ra.divisions * ra.chunks;
+    MGX_TRY(ensure(h, h->band, ((size_t)n_target + wgs * BAND_SLACK) * sizeof(float)));
+    MGX_TRY(ensure(h, h->band_info, wgs * sizeof(BandInfo)));
+    ra.band = (float*)h->band.p;
+    ra.info = (BandInfo*)h->band_info.p;
+    ra.reference_match_rms = &((const TrackStats*)rw.stats.p)->match_rms;
+    ra.eps = cfg->min_value;
+    ra.threshold = cfg->threshold;
+    ra.cs = cs;
+    ra.npeaks = nblocks;
+    MGX_TRY(ensure_ctrl(h));
+    ra.error = h->error_dev;
+    const size_t lds_step = (size_t)(64 + tw.divisions + (size_t)ra.divisions * ra.chunks) * sizeof(double);
+    if (lds_step > LDS_PER_WORKGROUP_MAX) return fail(MGX_ERR_UNSUPPORTED, TOO_MANY_PIECES);
+    MGX_TRY(allow_lds(k_correction_round, lds_step));
+    const int rounds = cfg->rms_correction_steps;
+    ra.lim_published = nullptr;
+    ra.lim_words = 0;
+    ra.lim_ticket = nullptr;
+    ra.tail_gains = use_tail ? (unsigned long long*)h->tail_gains.p : nullptr;
+    if (rounds >= 1) {                                    // round 0 streams the mid plane and builds the band lists
+        RoundArgs r0 = ra;
+        r0.final_peaks = rounds == 1 ? (const float*)h->block_peak.p : nullptr;    // (the launch of the last round)
+        r0.build_band = 1;
+        r0.step = 0;
+        if (lp) {     // the limiter's look-back words are preset by this grid: a thousand workgroups, two words a thread
+            MGX_TRY(limiter_state(h, n_target, *lp, &r0.lim_published, &r0.lim_words, &r0.lim_ticket));
+            *limiter_preset = true;
+        }
+        hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, r0);
+    }
+    if (rounds > 1 && !use_tail) {
+        // one launch per round, the last arriver of each decides (k_correction_round without a tail): what a handle
+        // falls back to after its tail kernel found the GPU shared (check_device_error), and MGX_NO_TAIL=1
+        for (int r = 1; r < rounds; ++r) {
+            RoundArgs rr = ra;
+            rr.build_band = 0;
+            rr.step = r;
+            rr.final_peaks = r == rounds - 1 ? (const float*)h->block_peak.p : nullptr;
+            hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, rr);
+        }
+    }
+    if (use_tail) {                                       // every further round inside one small resident grid
+        RoundArgs rt = ra;
+        rt.build_band = 0;
+        rt.step = 1;
+        rt.final_peaks = (const float*)h->block_peak.p;
+        const int groups = tail_groups;
+        const size_t lds_tail = correction_tail_lds_bytes(ra.divisions, groups, ra.chunks);
+        if (lds_tail > LDS_PER_WORKGROUP_MAX) return fail(MGX_ERR_UNSUPPORTED, TOO_MANY_PIECES);
+        MGX_TRY(allow_lds(k_correction_tail, lds_tail));
+        // (+ 1: the deciding workgroup)
+        hipLaunchKernelGGL(k_correction_tail, dim3(ra.divisions * groups + 1), dim3(256), lds_tail, h->stream, rt, groups,
+                           rounds - 1);
+    }
+    if (rounds == 0)
+        hipLaunchKernelGGL(k_finalize_scalars, dim3(1), dim3(256), 0, h->stream, (const float*)h->block_peak.p,
+                           nblocks, cfg->threshold, cfg->min_value, cs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // hold / release filters of order 2 or 3: k_limit_general<K>, its tables uploaded when the parameters change
 template <int K>
 static int launch_limiter_general(mgx_handle* h, const LimiterArgs& a, const LimiterParams& lp) {
@@ -991,7 +1003,7 @@ static int launch_limiter_general(mgx_handle* h, const LimiterArgs& a, const Lim
 // (a persistent grid that fetches a workgroup's next chunk under its current one was built and measured in round 4:
 // 187 against 171 us, profiles/r04_c_persistent_limiter.txt)
 // the 256-block kernel: the instantiation for the configuration's window geometry when there is one (k_limit in
-// mgx_kernels.h)
+// limiter_kernels.h)
 static void launch_limiter_256(const LimiterArgs& a, dim3 grid, hipStream_t stream) {
     const size_t lds = LimiterBlock<256>::LDS_BYTES;
 #ifdef MGX_TEST_LIMIT_GENERAL
@@ -1103,7 +1115,6 @@ static int run_limiter(mgx_handle* h, const float* y, long long n, const Limiter
 //     queued again with rounds 1..K-1 as one launch each (they wait for nobody), the handle stays that way, and the
 //     call succeeds; mgx_last_error() carries a note.
 //   * anything else (a limiter look-back word that never came): MGX_ERR_HIP.
-static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c);
 // `may_requeue`: the caller has not yet handed anything of the failed run to the host (master_impl before its report
 // is read, mgx_synchronize / mgx_stage_times with no download queued behind the call, the blocking copy that re-issues
 // itself).  Everywhere else -- and whenever MORE than one mgx_master call is outstanding since the last
@@ -1679,9 +1690,6 @@ int mgx_resample_plan(mgx_handle* h, int32_t rate_in, int32_t rate_out, void** w
 
 // ---- the boundary: stages.main ----------------------------------------------
 } // extern "C"
-static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
-                       int64_t n_reference, const mgx_config* cfg, const float* fir_given, float* result_dev,
-                       float* result_no_limiter_dev, float* result_no_limiter_normalized_dev, mgx_report* report);
 // every launch of one stages.main, queued on the handle's stream (no host round trip)
 static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     const float* target_dev = c.target;
@@ -1715,98 +1723,12 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     long long nblocks = 0;
     MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)h->taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
                      &nblocks, (const double*)h->scalars.p));
-    // stage 3 (stages.py:138-170): scalar feedback stays on the device; one launch per round, the last
-    // round also derives the peak / early-out / normalisation scalars (the state was reset by k_fir_raw)
+    // stage 3 (stages.py:138-170): scalar feedback stays on the device (the state was reset by k_fir_raw)
     CorrectionState* cs = (CorrectionState*)h->cstate.p;
     bool limiter_preset = false;
     {
         StageScope scope(h, MGX_STAGE_CORRECT_LEVELS);
-        RoundArgs ra;
-        ra.mid = (const float*)h->mid.p;
-        ra.piece = tw.piece;
-        ra.divisions = tw.divisions;
-        ra.chunks = std::max(1, 1024 / tw.divisions);     // ~1000 workgroups: each pays one publish + ticket
-        // (round 0's partial sums, and behind them the peak words of k_correction_tail's workgroups)
-        MGX_TRY(ensure(h, h->partial, (size_t)2 * ra.divisions * ra.chunks * sizeof(double)));
-        ra.partial = (double*)h->partial.p;
-        // arrival counters [1 + divisions], zero between launches; the 16 gain words of k_correction_tail
-        // live in their own buffer (a layout that moved with `divisions` would leave one call's preset
-        // gain words where the next call counts arrivals)
-        const size_t ctr_bytes = (size_t)(1 + ra.divisions) * sizeof(unsigned);
-        // at most ~128 workgroups in k_correction_tail, at most 64 chunks (the lanes of a wave) per workgroup
-        const int tail_groups = std::max((ra.chunks + 63) / 64, std::max(1, std::min(ra.chunks, 128 / ra.divisions)));
-        const bool use_tail = cfg->rms_correction_steps > 1 && !h->avoid_tail;
-        const int tail_total = use_tail ? ra.divisions * tail_groups : 0;
-        const int tail_rounds = use_tail ? cfg->rms_correction_steps - 1 : 0;
-        MGX_TRY(ensure(h, h->tail_gains, ((size_t)tail_rounds + 1 + (size_t)tail_rounds * tail_total) * sizeof(unsigned long long)));
-        ra.tail_total = tail_total;
-        ra.tail_rounds = tail_rounds;
-        if (h->round_ctr.bytes < ctr_bytes) {                 // zeroed when (re)allocated, reset by each launch
-            MGX_TRY(ensure(h, h->round_ctr, std::max(ctr_bytes, (size_t)4096)));
-            HIP_TRY(hipMemsetAsync(h->round_ctr.p, 0, h->round_ctr.bytes, h->stream));
-        }
-        ra.arrivals = (unsigned*)h->round_ctr.p;
-        const size_t wgs = (size_t)ra.divisions * ra.chunks;
-        MGX_TRY(ensure(h, h->band, ((size_t)n_target + wgs * BAND_SLACK) * sizeof(float)));
-        MGX_TRY(ensure(h, h->band_info, wgs * sizeof(BandInfo)));
-        ra.band = (float*)h->band.p;
-        ra.info = (BandInfo*)h->band_info.p;
-        ra.reference_match_rms = &((const TrackStats*)rw.stats.p)->match_rms;
-        ra.eps = cfg->min_value;
-        ra.threshold = cfg->threshold;
-        ra.cs = cs;
-        ra.npeaks = nblocks;
-        MGX_TRY(ensure_ctrl(h));
-        ra.error = h->error_dev;
-        const size_t lds_step = (size_t)(64 + tw.divisions + (size_t)ra.divisions * ra.chunks) * sizeof(double);
-        if (lds_step > LDS_PER_WORKGROUP_MAX)
-            return fail(MGX_ERR_UNSUPPORTED, "too many analysis pieces for the level-correction kernel's LDS");
-        MGX_TRY(allow_lds(k_correction_round, lds_step));
-        const int rounds = cfg->rms_correction_steps;
-        ra.lim_published = nullptr;
-        ra.lim_words = 0;
-        ra.lim_ticket = nullptr;
-        ra.tail_gains = use_tail ? (unsigned long long*)h->tail_gains.p : nullptr;
-        if (rounds >= 1) {                                    // round 0 streams the mid plane and builds the band lists
-            RoundArgs r0 = ra;
-            r0.final_peaks = rounds == 1 ? (const float*)h->block_peak.p : nullptr;    // (the launch of the last round)
-            r0.build_band = 1;
-            r0.step = 0;
-            if (result_dev) {     // the limiter's look-back words are preset by this grid: a thousand workgroups, two words a thread
-                MGX_TRY(limiter_state(h, n_target, c.lp, &r0.lim_published, &r0.lim_words, &r0.lim_ticket));
-                limiter_preset = true;
-            }
-            hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, r0);
-        }
-        if (rounds > 1 && !use_tail) {
-            // one launch per round, the last arriver of each decides (k_correction_round without a tail): what a handle
-            // falls back to after its tail kernel found the GPU shared (check_device_error), and MGX_NO_TAIL=1
-            for (int r = 1; r < rounds; ++r) {
-                RoundArgs rr = ra;
-                rr.build_band = 0;
-                rr.step = r;
-                rr.final_peaks = r == rounds - 1 ? (const float*)h->block_peak.p : nullptr;
-                hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, rr);
-            }
-        }
-        if (use_tail) {                                       // every further round inside one small resident grid
-            RoundArgs rt = ra;
-            rt.build_band = 0;
-            rt.step = 1;
-            rt.final_peaks = (const float*)h->block_peak.p;
-            const int groups = tail_groups;
-            const size_t lds_tail = correction_tail_lds_bytes(ra.divisions, groups, ra.chunks);
-            if (lds_tail > LDS_PER_WORKGROUP_MAX)
-                return fail(MGX_ERR_UNSUPPORTED, "too many analysis pieces for the level-correction kernel's LDS");
-            MGX_TRY(allow_lds(k_correction_tail, lds_tail));
-            // (+ 1: the deciding workgroup)
-            hipLaunchKernelGGL(k_correction_tail, dim3(ra.divisions * groups + 1), dim3(256), lds_tail, h->stream, rt, groups,
-                               rounds - 1);
-        }
-        if (rounds == 0)
-            hipLaunchKernelGGL(k_finalize_scalars, dim3(1), dim3(256), 0, h->stream, (const float*)h->block_peak.p,
-                               nblocks, cfg->threshold, cfg->min_value, cs);
-        HIP_TRY(hipGetLastError());
+        MGX_TRY(run_correction(h, cfg, tw, rw, n_target, nblocks, result_dev ? &c.lp : nullptr, &limiter_preset));
     }
     // stage 4 (stages.py:173-207)
     if (result_no_limiter_dev || result_no_limiter_normalized_dev) {
@@ -1936,8 +1858,6 @@ int mgx_stage_times(mgx_handle* h, float* ms) {
     return check_device_error(h);
 }
 
-}  // extern "C"
-extern "C" {
 int mgx_code_bytes(int32_t* bytes, int32_t capacity) {
     if (!bytes || capacity < CODE_KERNELS * CODE_VARIANTS) return fail(MGX_ERR_ARGUMENT, "need room for 7 x 16 sizes");
     int found[CODE_KERNELS][CODE_VARIANTS];

@@ -5,12 +5,13 @@
 // transform fits one thread's registers, and a 32-tap filter is applied in the time domain.
 //
 //   k_analyze_small<LOG2F>  match_levels.py:134-161 + match_frequencies.py:30-42, outputs as k_analyze
-//   k_fir_taps_direct       match_frequencies.py:98-99 (irfft, ifftshift, Hann) as a direct cosine sum (mgx_kernels.h)
+//   k_fir_taps_direct       match_frequencies.py:98-99 (irfft, ifftshift, Hann) as a direct cosine sum (fir_kernels.h)
 //   k_conv_direct           match_frequencies.py:104-119 (fftconvolve "same" on mid and side, ms_to_lr)
 #pragma once
 
 #include "analysis2_kernel.h"
 #include "fir_plan.h"
+#include "wave_util.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(fast)        // the float32 butterflies only, as in fft2.h

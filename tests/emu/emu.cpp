@@ -739,7 +739,7 @@ static int limit_impl(const LimiterParams& lp, const float* x, long long n, cons
     return ctrl[1] ? -2 : 0;
 }
 
-// hold / release filters of order up to K: limit_chunk_general of mgx_kernels.h, phase by phase
+// hold / release filters of order up to K: limit_chunk_general of limiter_kernels.h, phase by phase
 template <int K>
 static int limit_general_impl(const LimiterParams& lp, const float* x, long long n, const mgx_config* cfg, double gain,
                               double post_gain, float* out) {
@@ -873,7 +873,7 @@ extern "C" int emu_design_fir_direct(const mgx_config* cfg, const double* avg_ta
     design_fir_direct(avg_target, avg_reference, p, taps, curve_raw, curve_smooth);
     return 0;
 }
-// The raw -> smooth operator in its two factors through the LOWESS anchors (mgx.hip build_fir_factors, mgx_kernels.h
+// The raw -> smooth operator in its two factors through the LOWESS anchors (mgx.hip build_fir_factors, fir_kernels.h
 // k_fir_apply_a / k_fir_apply_b), with the phase functions the device kernels run: unit raw curves -> the anchors' fits
 // (A), unit fits -> the smooth curve (B), rows cut to the window above 1e-18 of their largest entry (k_fir_band), then
 // smooth = B (A raw) with bins 0 and 1 pinned.  Returns the windows' total sizes (in doubles) for the two factors.

@@ -81,7 +81,7 @@ def test_entry_points_that_need_no_device():
 
 def test_code_sizes_are_read_from_the_librarys_own_code_object():
     """mgx_code_bytes (no GPU needed): the windows the kernels' first workgroups read as data to put their own code
-    into the L2 (mgx_kernels.h, warm_code) come from the device ELF inside libmgx.so.  They must be there for the
+    into the L2 (wave_util.h, warm_code) come from the device ELF inside libmgx.so.  They must be there for the
     instantiations the benchmarks run, and no larger than the symbols llvm-readelf reports: a window that
     reaches past its kernel could reach past the end of the code object."""
     import ctypes

@@ -1,4 +1,4 @@
-"""The algebra k_correction_round / k_correction_tail rest on (csrc/mgx_kernels.h "band"), in
+"""The algebra k_correction_round / k_correction_tail rest on (csrc/correction_kernels.h "band"), in
 numpy: for an accumulated gain g in [0.7, 1.5] the sum stages.py:149-168 needs, sum clip(g * m)^2 (dsp.py:109-110),
 splits into g^2 * A + C + the band's own sum, with float32 thresholds rounded towards the inside of the band."""
 import numpy as np

@@ -195,7 +195,7 @@ def test_the_tail_test_build_is_not_the_product():
     from matchering_amd import build as native_build
 
     assert native_build.source_hash() != native_build.source_hash(TAIL_FLAGS)
-    with open(os.path.join(ROOT, "matchering_amd", "csrc", "mgx_kernels.h")) as fh:
+    with open(os.path.join(ROOT, "matchering_amd", "csrc", "correction_kernels.h")) as fh:
         text = fh.read()
     assert "#ifdef MGX_TEST_TAIL_EXPIRE" in text and "#ifdef MGX_TEST_TAIL_MAX_SPINS" in text
 

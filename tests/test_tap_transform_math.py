@@ -1,4 +1,4 @@
-"""The identities k_fir_taps_sub / k_fir_taps_combine (csrc/mgx_kernels.h) are built on, restated in numpy with the
+"""The identities k_fir_taps_sub / k_fir_taps_combine (csrc/fir_kernels.h) are built on, restated in numpy with the
 kernels' own index arithmetic and checked against numpy.fft.irfft -- what match_frequencies.py:98 calls.  The GPU
 parity of the taps themselves is tests/test_gpu_parity.py (golden fir_mid / fir_side, 8192 / 16384 / 32768 taps)."""
 import numpy as np
