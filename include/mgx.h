@@ -220,6 +220,57 @@ int mgx_master_with_fir(mgx_handle* h, const float* target_dev, int64_t n_target
                         float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
                         mgx_report* report);
 
+/* Reference profiles: everything stages.main takes from the reference track (stages.py:38-104: match_levels.py:29-44
+ * final_amplitude_coefficient, match_levels.py:134-161 reference_match_rms, match_frequencies.py:30-42 the loud pieces'
+ * average spectra of mid and side), analysed once and kept, so that any number of targets are mastered against it
+ * without its audio.  A profile is a plain block of device memory that the CALLER owns, mgx_profile_bytes(cfg) long:
+ *
+ *     mgx_profile_header                          (96 bytes, below)
+ *     double avg_mid [fft_size / 2 + 1]           mean |rfft| / fft_size over the loud pieces of the peak-normalised
+ *     double avg_side[fft_size / 2 + 1]           reference: what mgx_analyze(is_reference = 1) returns
+ *
+ * Nothing in it is a pointer or a handle and every field is little-endian as the GPU wrote it: mgx_memcpy_d2h keeps
+ * it, mgx_memcpy_h2d brings it back, on any handle and any GPU.  The library's own handling of a profile never waits for
+ * the device: mgx_reference_profile only queues, and mgx_master_with_profile waits exactly where mgx_master does (for a
+ * report).
+ * The header repeats the Config fields the analysis depends on.  A profile that does not fit the `cfg` it is used
+ * with -- another magic or version, or one of those five fields different -- is never used silently: the device finds
+ * out (the host could only by waiting), leaves the outputs of that call invalid, and the next blocking call on the
+ * handle fails with MGX_ERR_ARGUMENT and a message that names the field.  The handle is good for the next call. */
+#define MGX_PROFILE_MAGIC 0x5250474du    /* "MGPR" */
+#define MGX_PROFILE_VERSION 1u
+typedef struct mgx_profile_header {
+    uint32_t magic, version;
+    int32_t internal_sample_rate;        /* Config: defaults.py:61-84 */
+    int32_t fft_size;
+    double max_piece_size;               /* in samples, as in mgx_config */
+    double threshold;
+    double min_value;
+    int64_t frames;                      /* the reference: its length, */
+    int64_t piece;                       /* match_levels.py:47-59 piece size and count, */
+    int32_t divisions;
+    int32_t loud_count;                  /* match_levels.py:93-103: pieces at or above the average RMS */
+    double peak;                         /* dsp.py:97 */
+    double amplitude_coefficient;        /* match_levels.py:29-44 final_amplitude_coefficient */
+    double average_rms;                  /* match_levels.py:62-71, of the normalised reference */
+    double match_rms;                    /* match_levels.py:93-103 reference_match_rms */
+} mgx_profile_header;
+/* Size of a profile for `cfg` (header + 2 * (fft_size / 2 + 1) doubles).  Needs no GPU. */
+int mgx_profile_bytes(const mgx_config* cfg, size_t* bytes);
+/* The reference half of stages.py:38-104 (match_levels.py:134-161 analyze_levels with normalisation,
+ * match_frequencies.py:30-42 __average_fft): the analysis mgx_analyze(is_reference = 1) runs, its results packed into
+ * profile_dev.  Queued on the handle's stream.  A reference with NaN or infinite samples makes the next blocking call
+ * fail, as it does for mgx_master (match_frequencies.py:42). */
+int mgx_reference_profile(mgx_handle* h, const float* reference_dev, int64_t n_reference, const mgx_config* cfg,
+                          void* profile_dev);
+/* stages.py:210-272 `main` with the reference given as a profile: mgx_master, or mgx_master_with_fir when fir_dev is
+ * not NULL, with stage 1 run on the target alone.  A report's reference_* fields and final_amplitude_coefficient are
+ * the profile's.  Returns before the GPU has finished when report == NULL, as mgx_master does. */
+int mgx_master_with_profile(mgx_handle* h, const float* target_dev, int64_t n_target, const void* profile_dev,
+                            const mgx_config* cfg, const float* fir_dev, float* result_dev,
+                            float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
+                            mgx_report* report);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

@@ -15,3 +15,4 @@ from .core import process  # noqa: F401
 from .audio_io import load  # noqa: F401
 from .checker import check  # noqa: F401
 from .batch import master_many, process_batch  # noqa: F401  (no counterpart in the reference)
+from .profile import ReferenceProfile  # noqa: F401  (nor this: a reference analysed once, kept without its audio)

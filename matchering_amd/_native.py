@@ -65,6 +65,32 @@ class MgxReport(ctypes.Structure):
     ]
 
 
+class MgxProfileHeader(ctypes.Structure):
+    """mgx_profile_header (include/mgx.h): the fixed head of a reference profile; 2 * (fft_size / 2 + 1) float64 follow."""
+
+    _fields_ = [
+        ("magic", ctypes.c_uint32),
+        ("version", ctypes.c_uint32),
+        ("internal_sample_rate", ctypes.c_int32),
+        ("fft_size", ctypes.c_int32),
+        ("max_piece_size", ctypes.c_double),
+        ("threshold", ctypes.c_double),
+        ("min_value", ctypes.c_double),
+        ("frames", ctypes.c_int64),
+        ("piece", ctypes.c_int64),
+        ("divisions", ctypes.c_int32),
+        ("loud_count", ctypes.c_int32),
+        ("peak", ctypes.c_double),
+        ("amplitude_coefficient", ctypes.c_double),
+        ("average_rms", ctypes.c_double),
+        ("match_rms", ctypes.c_double),
+    ]
+
+
+PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
+PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
+
+
 # every symbol include/mgx.h declares: name -> (restype, argtypes)
 _VP = ctypes.c_void_p
 SYMBOLS = {
@@ -86,6 +112,10 @@ SYMBOLS = {
                                   _VP, _VP, _VP, ctypes.POINTER(MgxReport)]),
     "mgx_master_with_fir": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, ctypes.c_int64, ctypes.POINTER(MgxConfig),
                                            _VP, _VP, _VP, _VP, ctypes.POINTER(MgxReport)]),
+    "mgx_profile_bytes": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(ctypes.c_size_t)]),
+    "mgx_reference_profile": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxConfig), _VP]),
+    "mgx_master_with_profile": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, ctypes.POINTER(MgxConfig), _VP,
+                                               _VP, _VP, _VP, ctypes.POINTER(MgxReport)]),
     "mgx_analyze": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxConfig), ctypes.c_int,
                                    c_double_p, c_double_p, c_double_p, c_int32_p, c_int64_p,
                                    c_double_p, c_int32_p, c_double_p, c_double_p]),
@@ -132,6 +162,7 @@ STAGES = ("analyze", "design_fir", "filter_spectra", "convolve", "correct_levels
 
 ERR_RETRY = -6          # enum mgx_status MGX_ERR_RETRY (include/mgx.h)
 ERR_UNSUPPORTED = -4    # ... MGX_ERR_UNSUPPORTED
+ERR_ARGUMENT = -1       # ... MGX_ERR_ARGUMENT
 
 
 class MgxError(RuntimeError):

@@ -27,7 +27,8 @@ and on a node with 8 GPUs::
         -m matchering_amd.batch jobs.json
 
 ``jobs.json`` is a list of ``{"target": path, "reference": path, "results": [{"file": path,
-"subtype": "PCM_16", "use_limiter": true, "normalize": true}, ...]}``.
+"subtype": "PCM_16", "use_limiter": true, "normalize": true}, ...]}``; in place of ``"reference"`` a job may name a
+``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py).
 """
 
 import json
@@ -40,7 +41,7 @@ import numpy as np
 from concurrent.futures import ThreadPoolExecutor
 
 from .config import Config
-from .log import Code, ModuleError
+from .log import Code, ModuleError, debug
 from .results import Result
 
 
@@ -268,7 +269,8 @@ def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
     """``stages.main`` over a list of (target, reference) arrays on ONE GPU, ``lanes`` pairs in flight
     (``None``: as many as ``choose_lanes`` measures to be best on this GPU).
 
-    Returns the list of result triples in the order of ``pairs``.  Results are bit-identical to
+    A pair's reference may be a ``profile.ReferenceProfile`` (uploaded once per lane device).  Returns the list of
+    result triples in the order of ``pairs``.  Results are bit-identical to
     calling ``stages.main`` pair by pair: lanes only change when work is submitted, never what is
     computed.  With ``on_result(index, triple)`` every triple is handed over as it completes (from a lane
     thread) and NOT kept: the pinned host blocks the results live in are recycled as soon as the
@@ -301,7 +303,8 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     (2 x fft_size float32, 32 KiB at the default size) is the only thing that crosses xGMI -- one
     ``ncclBroadcast`` over RCCL -- and every rank then masters its share of the targets (track i -> rank
     i mod world) with that FIR given (``mgx_master_with_fir``), levels still matched per track.  Returns
-    ``{index: triple}`` for this rank's tracks.  ``exchange(payload, size)`` must hand rank 0's 128-byte
+    ``{index: triple}`` for this rank's tracks.  ``reference`` may be a ``profile.ReferenceProfile``: the reference
+    is then never uploaded or analysed here (``mgx_master_with_profile``).  ``exchange(payload, size)`` must hand rank 0's 128-byte
     RCCL id to all ranks (bench.Ranks.broadcast_bytes); not needed with one rank."""
     from .stages import main
 
@@ -336,6 +339,40 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     return results
 
 
+class _SharedReference:
+    """``process_batch(share_references=True)``: the reference FILE of a job, left to the lane that masters the job --
+    which analyses it once (``ReferenceProfile.analyze``) and masters every job that names the same file against
+    that profile."""
+
+    def __init__(self, path):
+        self.path = path
+
+    @property
+    def key(self):
+        try:
+            st = os.stat(self.path)
+            return (st.st_dev, st.st_ino)              # (what os.path.samefile compares)
+        except OSError:
+            return os.path.abspath(self.path)
+
+
+def _analyze_reference(path, config, device):
+    from .profile import ReferenceProfile
+
+    return ReferenceProfile.analyze(path, config, device=device)
+
+
+def _job_profile(job):
+    """The ``ReferenceProfile`` of a job that names one ("reference_profile": the object or a saved file), else None."""
+    from .profile import ReferenceProfile
+
+    _job_reference_keys(job)
+    given = job.get("reference_profile")
+    if given is None:
+        return None
+    return given if isinstance(given, ReferenceProfile) else ReferenceProfile.load(given)
+
+
 class _Later:
     """What ``_load_job`` left to the lane that masters the job, per track the file's rate when the track is still
     as its file holds it (None: it is the final track already)."""
@@ -361,7 +398,7 @@ def _on_the_lane(target, reference, later, device_index, lane, config, master):
     try:
         with dev.lock:
             for slot, (audio, rate) in enumerate(((target, later.target_rate), (reference, later.reference_rate))):
-                if rate is not None:
+                if rate is not None:                   # (never a profile's: _load_job leaves its rate None)
                     on_device[slot] = dev.track_frames(audio, rate, internal)
             if on_device[0] is not None:
                 peaks = dev.peak_count(on_device[0], 2 * on_device[0].frames)
@@ -399,9 +436,12 @@ def _needs_of(results):
             any(not r.use_limiter and r.normalize for r in results))
 
 
-def _load_job(job, config, gpu=False):
+def _load_job(job, config, gpu=False, shared=False):
     """Load + check both files of a job (core.py:52-74), on a host thread.  Returns (target, reference,
-    later): with ``later`` (a ``_Later``) a track is still as its file holds it and goes to the GPU that way.  The
+    later): with ``later`` (a ``_Later``) a track is still as its file holds it and goes to the GPU that way.  A job
+    with a "reference_profile", or whose reference file is ``shared`` with other jobs (``process_batch``'s
+    ``share_references``), loads its target only: ``reference`` is then the ``ReferenceProfile`` / a
+    ``_SharedReference``, and the equality check of checker.py:140-142, which needs the reference's audio, is not made.  The
     target's peak statistics (checker.py:118-130) are then left to the lane that masters it (``mgx_peak_count``),
     and with ``gpu`` so is the conversion of a mono or off-rate track (``device.takes_resident``, the rule
     ``core.process`` uses): a loader thread never spends seconds in the host resampler while its lane idles."""
@@ -429,6 +469,19 @@ def _load_job(job, config, gpu=False):
     deferred, frames_t = on_the_lane(target, rate_t)
     convert_t = deferred and _changes(target, rate_t, internal)
     target, rate_t = check(target, rate_t, config, "target", peaks=LATER if deferred else None, on_device=convert_t)
+    profile = _job_profile(job)
+    if profile is not None or shared:
+        if profile is not None:
+            profile.matches(config)
+        frames_t = frames_t if convert_t else target.shape[0]
+        if rate_t != internal or not (convert_t or pcm_channels(target) == 2) or not frames_t > config.fft_size:
+            raise ModuleError(Code.ERROR_VALIDATION)
+        if not config.allow_equality:
+            from .core import NO_EQUALITY_CHECK
+
+            debug(NO_EQUALITY_CHECK)
+        stand_in = profile if profile is not None else _SharedReference(job["reference"])
+        return target, stand_in, (_Later(file_rate_t, None, False) if deferred else None)
     reference, rate_r = load(job["reference"], "reference", temp_folder, pcm=True)
     file_rate_r = rate_r
     convert_r, frames_r = on_the_lane(reference, rate_r)
@@ -462,10 +515,14 @@ def _save_job(job, triple, config):
 
 
 def process_batch(jobs, config=None, rank=None, world_size=None, device_index=None, lanes=None, io_threads=4,
-                  master=None):
+                  master=None, share_references=False):
     """``process`` for a list of jobs, this rank's share only.
 
-    ``jobs``: dicts with "target", "reference" (paths) and "results" (list of ``Result``).  Returns
+    ``jobs``: dicts with "target", "reference" (paths) and "results" (list of ``Result``); in place of "reference" a
+    job may name a "reference_profile" (a ``ReferenceProfile`` or the path of a saved one).  With
+    ``share_references=True`` the jobs of this rank that name the same reference FILE (``os.path.samefile``) have it
+    loaded and analysed once per lane device and are mastered against that profile.  Off by default: the profile
+    route agrees with the pair route to the project's tolerances, not bit for bit.  Returns
     the indices of the jobs this rank mastered.  The first failing job aborts the rank's batch and
     its exception is re-raised (after the jobs already in flight have finished)."""
     config = config if config is not None else Config()
@@ -476,13 +533,31 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
             raise RuntimeError("The result list is empty")
     device_index = local if device_index is None else device_index
     savers = []
+    shared_keys = set()
+    if share_references:
+        seen = {}
+        for i in mine:
+            if jobs[i].get("reference") is not None and jobs[i].get("reference_profile") is None:
+                key = _SharedReference(jobs[i]["reference"]).key
+                seen[key] = seen.get(key, 0) + 1
+        shared_keys = {key for key, count in seen.items() if count > 1}
+
+    def is_shared(job):
+        return bool(shared_keys) and job.get("reference") is not None and job.get("reference_profile") is None \
+            and _SharedReference(job["reference"]).key in shared_keys
 
     with ThreadPoolExecutor(max_workers=max(1, io_threads)) as io:
         def worker_for(lane):
             workers = {}
+            profiles = {}                              # share_references: reference file -> its profile on this lane
 
             def run(item):
                 index, (target, reference, later) = item
+                if isinstance(reference, _SharedReference):
+                    if reference.key not in profiles:
+                        profiles[reference.key] = _analyze_reference(
+                            reference.path, config, None if master is not None else lane_device(device_index, lane))
+                    reference = profiles[reference.key]
                 needs = _needs_of(jobs[index]["results"])
                 key = (needs, _wanted_encodings(jobs[index]["results"]))
                 if key not in workers:
@@ -508,13 +583,14 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                 future.add_done_callback(lambda _f: unsaved.release())
                 savers.append(future)
 
-        ahead = {k: io.submit(_load_job, jobs[i], config, master is None) for k, i in enumerate(mine[:io_threads])}
+        ahead = {k: io.submit(_load_job, jobs[i], config, master is None, is_shared(jobs[i]))
+                 for k, i in enumerate(mine[:io_threads])}
         nxt = len(ahead)
         try:
             for k, i in enumerate(mine):
                 arrays = ahead.pop(k).result()            # (popped: the decoded arrays live on only in the job)
                 if nxt < len(mine):
-                    ahead[nxt] = io.submit(_load_job, jobs[mine[nxt]], config, master is None)
+                    ahead[nxt] = io.submit(_load_job, jobs[mine[nxt]], config, master is None, is_shared(jobs[mine[nxt]]))
                     nxt += 1
                 pool.submit(i, (i, arrays), done)
                 del arrays
@@ -538,8 +614,21 @@ def jobs_from_json(path):
     for item in raw:
         results = [Result(r["file"], subtype=r.get("subtype", "PCM_16"), use_limiter=r.get("use_limiter", True),
                           normalize=r.get("normalize", True)) for r in item["results"]]
-        jobs.append({"target": item["target"], "reference": item["reference"], "results": results})
+        job = {"target": item["target"], "results": results}
+        for key in ("reference", "reference_profile"):
+            if item.get(key) is not None:
+                job[key] = item[key]
+        _job_reference_keys(job)
+        jobs.append(job)
     return jobs
+
+
+def _job_reference_keys(job):
+    """A job names its reference exactly once: "reference" (an audio file) or "reference_profile" (a saved profile)."""
+    named = [key for key in ("reference", "reference_profile") if job.get(key) is not None]
+    if len(named) != 1:
+        raise ValueError(f'job for {job.get("target")!r}: exactly one of "reference" and "reference_profile" is needed, '
+                         f'got {named or "neither"}')
 
 
 def main(argv=None):

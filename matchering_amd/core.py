@@ -122,6 +122,50 @@ def _read_pair(target_path, reference_path, config, temp_folder):
     return target, reference, resident
 
 
+def _as_profile(reference):
+    """The ``ReferenceProfile`` that ``process`` was given in the reference's place -- the object itself, or the path of
+    a saved one, recognised by the file's magic and not by its name -- or None for an audio file."""
+    from .profile import ReferenceProfile, is_profile_file
+
+    if isinstance(reference, ReferenceProfile):
+        return reference
+    if isinstance(reference, (str, bytes, os.PathLike)) and is_profile_file(reference):
+        return ReferenceProfile.load(reference)
+    return None
+
+
+NO_EQUALITY_CHECK = ("the reference is a profile, not audio: whether it was made from the target itself "
+                     "(checker.py:140-142) cannot be checked and is not")
+
+
+def read_track(path, role, config, temp_folder, dev):
+    """``_read_pair`` for ONE track in the given role (its partner is a profile, or it is becoming one): loaded,
+    taken resident where ``device.takes_resident`` says so (the target's peak statistics then come from the GPU),
+    checked and validated as core.py:52-74 does.  Returns (checked array, resident ``DeviceFrames`` or None)."""
+    from .device import takes_resident
+
+    internal = config.internal_sample_rate
+    audio, rate = load(path, role, temp_folder, pcm=True)
+    peaks, frames = None, None
+    if dev is not None and takes_resident(audio, rate, internal):
+        with dev.lock:
+            frames = dev.track_frames(audio, rate, internal)
+            if role == "target":
+                peaks = dev.peak_count(frames, 2 * frames.frames)
+    changed = frames is not None and (rate != internal or pcm_channels(audio) != 2)
+    try:
+        array, checked_rate = check(audio, rate, config, role, peaks=peaks, on_device=changed)
+        length = frames.frames if changed else array.shape[0]
+        channels = 2 if changed else pcm_channels(array)
+        if checked_rate != internal or channels != 2 or length <= config.fft_size:
+            raise ModuleError(Code.ERROR_VALIDATION)
+    except Exception:
+        if frames is not None:
+            frames.release()
+        raise
+    return array, frames
+
+
 def _same_file(a, b):
     try:
         return os.path.exists(a) and os.path.samefile(a, b)
@@ -147,7 +191,16 @@ def process(target: str, reference: str, results: list, config: Config = None,
         raise RuntimeError("The result list is empty")
     temp_folder = config.temp_folder or get_temp_folder(results)
 
-    target_audio, reference_audio, resident = _read_pair(target, reference, config, temp_folder)
+    profile = _as_profile(reference)
+    if profile is not None:
+        # the reference is a profile: only the target is loaded and checked
+        profile.matches(config)
+        target_audio, frames = read_track(target, "target", config, temp_folder, _gpu())
+        reference_audio, resident = profile, [frames, profile]
+        if not config.allow_equality:
+            debug(NO_EQUALITY_CHECK)
+    else:
+        target_audio, reference_audio, resident = _read_pair(target, reference, config, temp_folder)
     previews = bool(preview_target or preview_result)
     # With a GPU the previews are cut on it from the frames stages.main leaves in HBM (preview.PreviewRequest):
     # only the two 30 s pieces cross PCIe, and the renderings keep their integer encodings.  Without one (the

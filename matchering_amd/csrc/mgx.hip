@@ -160,6 +160,7 @@ struct mgx_handle {
         const float* target = nullptr;
         const float* reference = nullptr;
         const float* fir_given = nullptr;
+        const mgx_profile_header* profile = nullptr;     // mgx_master_with_profile: the reference is this, `reference` null
         int64_t n_target = 0, n_reference = 0;
         mgx_config cfg;
         LimiterParams lp;                   // derived from cfg when out[0] (the limited result) is wanted
@@ -243,8 +244,9 @@ static int ensure_ctrl(mgx_handle* h);
 // the boundary around it
 static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c);
 static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
-                       int64_t n_reference, const mgx_config* cfg, const float* fir_given, float* result_dev,
-                       float* result_no_limiter_dev, float* result_no_limiter_normalized_dev, mgx_report* report);
+                       int64_t n_reference, const mgx_profile_header* profile, const mgx_config* cfg,
+                       const float* fir_given, float* result_dev, float* result_no_limiter_dev,
+                       float* result_no_limiter_normalized_dev, mgx_report* report);
 
 static int get_twiddles(mgx_handle* h, int log2n, const float2** out) {
     auto it = h->twiddles.find(log2n);
@@ -572,9 +574,77 @@ static int build_fir_factors(mgx_handle* h, const FirPlanView& pl, PlanDev& pd) 
     return 0;
 }
 
-// fir_given: a FIR pair to use instead of the designed one (album mode), or null
+static ProfileWant profile_want(const mgx_config* cfg) {
+    return ProfileWant{cfg->internal_sample_rate, cfg->fft_size, cfg->max_piece_size, cfg->threshold, cfg->min_value};
+}
+
+// The raw matching curve of a target against a reference PROFILE (mgx_master_with_profile): k_profile_curve, one launch,
+// while the target's piece tables fit a workgroup's LDS -- its own carve, the target's rows only -- else k_levels +
+// k_average_spectra on the target and k_profile_raw.  Leaves what the pair route's curve kernels leave.
+static int run_profile_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanView& pl, const TrackWork& tw,
+                             const mgx_profile_header* profile, double* raw) {
+    const ProfileWant want = profile_want(cfg);
+    const size_t lds_curve = profile_curve_lds_bytes(tw.divisions, tw.nwg);
+    if (lds_curve <= LDS_PER_WORKGROUP_MAX) {
+        CurveTrack ct{levels_args(tw), (const float*)tw.wg_spec.p, tw.nwg, tw.segs_per_piece};
+        // (the 32 / 33 tile choice of the pair route: the grid has the same shape)
+        auto rounds = [&](int tile) { return (2 * ((pl.bins + tile - 1) / tile) + h->cus - 1) / h->cus; };
+        const int tile = rounds(33) < rounds(32) ? 33 : 32;
+        const auto curve = tile == 33 ? k_profile_curve<33> : k_profile_curve<32>;
+        MGX_TRY(allow_lds(curve, lds_curve));
+        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->stream, ct, profile, want,
+                           pl.bins, pl.fft, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)h->scalars.p,
+                           (CorrectionState*)h->cstate.p, h->error_dev);
+    } else {
+        TrackWork& t = const_cast<TrackWork&>(tw);
+        MGX_TRY(run_levels(h, cfg, &t, nullptr));
+        hipLaunchKernelGGL(k_profile_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->stream, pl,
+                           (const double*)tw.part.p, (const TrackStats*)tw.stats.p, tw.segs_per_piece, profile, want,
+                           cfg->min_value, raw, (double*)h->scalars.p, (CorrectionState*)h->cstate.p, h->error_dev);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The raw matching curve of a pair: piece decisions of both tracks, loud-piece spectra and the curve in one launch while
+// the piece tables fit a workgroup's LDS (always, short of thousands of pieces), three otherwise.
+static int run_pair_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanView& pl, const TrackWork& tw,
+                          const TrackWork& rw, double* raw) {
+    const int max_div = std::max(tw.divisions, rw.divisions);
+    const size_t lds_curve = match_curve_lds_bytes(max_div, tw.nwg + rw.nwg);
+    if (lds_curve <= LDS_PER_WORKGROUP_MAX) {
+        CurveTrack ct{levels_args(tw), (const float*)tw.wg_spec.p, tw.nwg, tw.segs_per_piece};
+        CurveTrack cr{levels_args(rw), (const float*)rw.wg_spec.p, rw.nwg, rw.segs_per_piece};
+        // tiles of 33 bins where they save a round of workgroups (one workgroup of 1024 threads per CU)
+        auto rounds = [&](int tile) { return (2 * ((pl.bins + tile - 1) / tile) + h->cus - 1) / h->cus; };
+        const int tile = rounds(33) < rounds(32) ? 33 : 32;
+        const auto curve = tile == 33 ? k_match_curve<33> : k_match_curve<32>;
+        MGX_TRY(allow_lds(curve, lds_curve));
+        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->stream, ct, cr, pl.bins,
+                           pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)h->scalars.p,
+                           (CorrectionState*)h->cstate.p, h->error_dev);
+    } else {
+        TrackWork& t = const_cast<TrackWork&>(tw);
+        TrackWork& r = const_cast<TrackWork&>(rw);
+        MGX_TRY(run_levels(h, cfg, &t, &r));
+        FirInputs in;
+        in.part_t = (const double*)tw.part.p;
+        in.part_r = (const double*)rw.part.p;
+        in.st_t = (const TrackStats*)tw.stats.p;
+        in.st_r = (const TrackStats*)rw.stats.p;
+        in.segs_t = tw.segs_per_piece;
+        in.segs_r = rw.segs_per_piece;
+        in.eps = cfg->min_value;
+        hipLaunchKernelGGL(k_fir_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->stream, pl, in, raw,
+                           (double*)h->scalars.p, (CorrectionState*)h->cstate.p);
+    }
+    return 0;
+}
+
+// fir_given: a FIR pair to use instead of the designed one (album mode), or null.  profile: the reference as a profile
+// (then `rw` is not looked at), or null
 static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const TrackWork& rw,
-                          const float* fir_given) {
+                          const float* fir_given, const mgx_profile_header* profile = nullptr) {
     FirDesignParams p{cfg->fft_size, cfg->internal_sample_rate, cfg->lin_log_oversampling, cfg->lowess_frac,
                       cfg->lowess_it, cfg->lowess_delta, cfg->min_value};
     std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(p);
@@ -620,41 +690,13 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     MGX_TRY(ensure(h, h->fir_scratch, (2 * per + 2 * (size_t)pl.bins + 2 * (size_t)pl.fft + 2) * sizeof(double)));
     MGX_TRY(ensure(h, h->scalars, 64));
     MGX_TRY(ensure(h, h->taps, (size_t)2 * cfg->fft_size * sizeof(float)));
-    FirInputs in;
-    in.part_t = (const double*)tw.part.p;
-    in.part_r = (const double*)rw.part.p;
-    in.st_t = (const TrackStats*)tw.stats.p;
-    in.st_r = (const TrackStats*)rw.stats.p;
-    in.segs_t = tw.segs_per_piece;
-    in.segs_r = rw.segs_per_piece;
-    in.eps = cfg->min_value;
     double* scratch = (double*)h->fir_scratch.p;
     double* raw = scratch + 2 * per;
     MGX_TRY(ensure(h, h->cstate, sizeof(CorrectionState)));
-    // piece decisions of both tracks, loud-piece spectra and the raw curve: one launch while the piece
-    // tables fit a workgroup's LDS (always, short of thousands of pieces), three otherwise
-    const int max_div = std::max(tw.divisions, rw.divisions);
-    const size_t lds_curve = match_curve_lds_bytes(max_div, tw.nwg + rw.nwg);
-    if (lds_curve <= LDS_PER_WORKGROUP_MAX) {
-        CurveTrack ct{levels_args(tw), (const float*)tw.wg_spec.p, tw.nwg, tw.segs_per_piece};
-        CurveTrack cr{levels_args(rw), (const float*)rw.wg_spec.p, rw.nwg, rw.segs_per_piece};
-        // tiles of 33 bins where they save a round of workgroups (one workgroup of 1024 threads per CU)
-        auto rounds = [&](int tile) { return (2 * ((pl.bins + tile - 1) / tile) + h->cus - 1) / h->cus; };
-        const int tile = rounds(33) < rounds(32) ? 33 : 32;
-        const auto curve = tile == 33 ? k_match_curve<33> : k_match_curve<32>;
-        MGX_TRY(allow_lds(curve, lds_curve));
-        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->stream, ct, cr, pl.bins,
-                           pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)h->scalars.p,
-                           (CorrectionState*)h->cstate.p, h->error_dev);
-    } else {
-        TrackWork& t = const_cast<TrackWork&>(tw);
-        TrackWork& r = const_cast<TrackWork&>(rw);
-        MGX_TRY(run_levels(h, cfg, &t, &r));
-        in.part_t = (const double*)tw.part.p;
-        in.part_r = (const double*)rw.part.p;
-        hipLaunchKernelGGL(k_fir_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->stream, pl, in, raw,
-                           (double*)h->scalars.p, (CorrectionState*)h->cstate.p);
-    }
+    if (profile)
+        MGX_TRY(run_profile_curve(h, cfg, pl, tw, profile, raw));
+    else
+        MGX_TRY(run_pair_curve(h, cfg, pl, tw, rw, raw));
     if (fir_given) {             // the levels above are this pair's own; the matching EQ is somebody else's
         if (fir_given != (const float*)h->taps.p)
             HIP_TRY(hipMemcpyAsync(h->taps.p, fir_given, (size_t)2 * cfg->fft_size * sizeof(float),
@@ -890,8 +932,9 @@ static const char* const TOO_MANY_PIECES = "too many analysis pieces for the lev
 // Stage 3 (stages.py:138-170), every round queued on the handle's stream: one launch per round, the last round also
 // derives the peak / early-out / normalisation scalars.  `nblocks`: the per-pair peaks the convolution left in
 // h->block_peak.  `lp`: the limiter's parameters when a limited result follows, else null; round 0's grid then presets
-// the limiter's look-back words (`*limiter_preset`).
-static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const TrackWork& rw,
+// the limiter's look-back words (`*limiter_preset`).  `reference_match_rms`: device address of the reference's match RMS
+// (the reference's TrackStats, or a profile's header).
+static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const double* reference_match_rms,
                           long long n_target, long long nblocks, const LimiterParams* lp, bool* limiter_preset) {
     CorrectionState* cs = (CorrectionState*)h->cstate.p;
     RoundArgs ra;
@@ -924,7 +967,7 @@ static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     MGX_TRY(ensure(h, h->band_info, wgs * sizeof(BandInfo)));
     ra.band = (float*)h->band.p;
     ra.info = (BandInfo*)h->band_info.p;
-    ra.reference_match_rms = &((const TrackStats*)rw.stats.p)->match_rms;
+    ra.reference_match_rms = reference_match_rms;
     ra.eps = cfg->min_value;
     ra.threshold = cfg->threshold;
     ra.cs = cs;
@@ -1132,13 +1175,25 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
     if (!h->error_host) return 0;
     volatile int* e = (volatile int*)h->error_host;
     const int what = (e[DEVICE_ERROR_SLOT_LOOKBACK] ? DEVICE_ERROR_LOOKBACK : 0) | (e[DEVICE_ERROR_SLOT_TAIL] ? DEVICE_ERROR_TAIL : 0) |
-                     (e[DEVICE_ERROR_SLOT_INPUT] ? DEVICE_ERROR_INPUT : 0);
+                     (e[DEVICE_ERROR_SLOT_INPUT] ? DEVICE_ERROR_INPUT : 0) | (e[DEVICE_ERROR_SLOT_PROFILE] ? DEVICE_ERROR_PROFILE : 0);
     if (what == 0) return 0;
+    const int profile_field = e[DEVICE_ERROR_SLOT_PROFILE];
     for (int i = 0; i < DEVICE_ERROR_SLOTS; ++i) e[i] = 0;
     if (h->round_ctr.p) HIP_TRY(hipMemsetAsync(h->round_ctr.p, 0, h->round_ctr.bytes, h->stream));
     if (h->lim_ctrl.p) HIP_TRY(hipMemsetAsync(h->lim_ctrl.p, 0, 64, h->stream));
     if (h->conv_queue.p) HIP_TRY(hipMemsetAsync(h->conv_queue.p, 0, 64, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    if (what & DEVICE_ERROR_PROFILE) {
+        // (before the input report: a profile that was not read makes no statement about anybody's samples)
+        static const char* const FIELDS[] = {"", "magic", "version", "internal_sample_rate", "fft_size", "max_piece_size",
+                                             "threshold", "min_value"};
+        const char* field = profile_field > 0 && profile_field < 8 ? FIELDS[profile_field] : "header";
+        return fail(MGX_ERR_ARGUMENT, std::string("the reference profile does not fit this call: its ") + field +
+                                      (profile_field <= PROFILE_BAD_VERSION
+                                           ? " is not that of a profile this library writes (mgx_profile_header)"
+                                           : " differs from the Config's; a profile is used with the Config it was made with") +
+                                      "; the outputs of the calls since the last synchronisation are not valid");
+    }
     if (what & DEVICE_ERROR_INPUT)
         return fail(MGX_ERR_ARGUMENT, "the target or the reference holds samples that are not finite numbers (NaN or infinity): "
                                       "the reference fails on such input too (match_frequencies.py:42)");
@@ -1187,7 +1242,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
 // ---------------------------------------------------------------------------
 extern "C" {
 
-int mgx_version(void) { return 101; }
+int mgx_version(void) { return 102; }
 const char* mgx_last_error(void) { return g_error.c_str(); }
 
 int mgx_device_count(int* count) {
@@ -1701,22 +1756,32 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     float* result_no_limiter_dev = c.out[1];
     float* result_no_limiter_normalized_dev = c.out[2];
     const int f = cfg->fft_size;
-    // stage 1 (stages.py:38-104): both tracks analysed in one pass each
+    // stage 1 (stages.py:38-104): both tracks analysed in one pass each -- or the target alone, against a profile
     TrackWork& tw = h->track[0];
     TrackWork& rw = h->track[1];
+    const mgx_profile_header* profile = c.profile;
+    // where stages 3 and 4 read the reference's two scalars: its TrackStats, or the profile's header
+    const double* reference_match_rms = profile ? &profile->match_rms : nullptr;
+    const double* reference_amplitude_c = profile ? &profile->amplitude_coefficient : nullptr;
     // (analysing the reference first, so that the target is the fresher track in the Infinity Cache when
     // the convolution reads it, was measured: no difference)
     {
         StageScope scope(h, MGX_STAGE_ANALYZE);
         tw.is_reference = 0;
-        rw.is_reference = 1;
-        MGX_TRY(run_analysis(h, cfg, target_dev, n_target, tw, reference_dev, n_reference, &rw));
+        if (profile) {
+            MGX_TRY(run_analysis(h, cfg, target_dev, n_target, tw));
+        } else {
+            rw.is_reference = 1;
+            MGX_TRY(run_analysis(h, cfg, target_dev, n_target, tw, reference_dev, n_reference, &rw));
+            reference_match_rms = &((const TrackStats*)rw.stats.p)->match_rms;      // (allocated by the line above)
+            reference_amplitude_c = &((const TrackStats*)rw.stats.p)->amplitude_c;
+        }
     }
     // stage 2 (stages.py:107-135): FIR design on the device, then the overlap-save convolution with
     // the level gain of stages.py:80-88 (a device scalar) folded into the filter spectra
     {
         StageScope scope(h, MGX_STAGE_DESIGN_FIR);
-        MGX_TRY(run_fir_design(h, cfg, tw, rw, fir_given));
+        MGX_TRY(run_fir_design(h, cfg, tw, rw, fir_given, profile));
     }
     MGX_TRY(ensure(h, h->y, (size_t)n_target * sizeof(float2)));
     MGX_TRY(ensure(h, h->mid, (size_t)n_target * sizeof(float)));
@@ -1728,7 +1793,8 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     bool limiter_preset = false;
     {
         StageScope scope(h, MGX_STAGE_CORRECT_LEVELS);
-        MGX_TRY(run_correction(h, cfg, tw, rw, n_target, nblocks, result_dev ? &c.lp : nullptr, &limiter_preset));
+        MGX_TRY(run_correction(h, cfg, tw, reference_match_rms, n_target, nblocks, result_dev ? &c.lp : nullptr,
+                               &limiter_preset));
     }
     // stage 4 (stages.py:173-207)
     if (result_no_limiter_dev || result_no_limiter_normalized_dev) {
@@ -1741,17 +1807,19 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     }
     if (result_dev) {
         StageScope scope(h, MGX_STAGE_LIMIT);
-        const double* post = &((const TrackStats*)rw.stats.p)->amplitude_c;
-        MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, c.lp, cfg->threshold, &cs->gain, post, &cs->limiter_active,
+        MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, c.lp, cfg->threshold, &cs->gain, reference_amplitude_c,
+                            &cs->limiter_active,
                             result_dev, limiter_preset));
     }
     return 0;
 }
 
+// the reference: `reference_dev` (n_reference frames), or `profile` with reference_dev null
 static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
-                       int64_t n_reference, const mgx_config* cfg, const float* fir_given, float* result_dev,
-                       float* result_no_limiter_dev, float* result_no_limiter_normalized_dev, mgx_report* report) {
-    if (!h || !target_dev || !reference_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+                       int64_t n_reference, const mgx_profile_header* profile, const mgx_config* cfg,
+                       const float* fir_given, float* result_dev, float* result_no_limiter_dev,
+                       float* result_no_limiter_normalized_dev, mgx_report* report) {
+    if (!h || !target_dev || (!reference_dev && !profile)) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(check_config(cfg));
     HIP_TRY(hipSetDevice(h->device));
     LimiterParams lp{};
@@ -1765,6 +1833,7 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
     call.target = target_dev;
     call.reference = reference_dev;
     call.fir_given = fir_given;
+    call.profile = profile;
     call.n_target = n_target;
     call.n_reference = n_reference;
     call.cfg = *cfg;
@@ -1782,16 +1851,29 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
         char* pin = (char*)h->pinned;
         TrackStats* st_t = (TrackStats*)pin;
         TrackStats* st_r = (TrackStats*)(pin + 256);
+        mgx_profile_header* hd_r = (mgx_profile_header*)(pin + 2048);       // (the profile route's reference)
         CorrectionState* hc = (CorrectionState*)(pin + 512);
         double* c0 = (double*)(pin + 1024);
         for (int attempt = 0; attempt < 2; ++attempt) {      // (a second time when the check queued the call again)
             HIP_TRY(hipMemcpyAsync(st_t, tw.stats.p, sizeof(TrackStats), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(st_r, rw.stats.p, sizeof(TrackStats), hipMemcpyDeviceToHost, h->stream));
+            if (profile)
+                HIP_TRY(hipMemcpyAsync(hd_r, profile, sizeof(mgx_profile_header), hipMemcpyDeviceToHost, h->stream));
+            else
+                HIP_TRY(hipMemcpyAsync(st_r, rw.stats.p, sizeof(TrackStats), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(hc, cs, sizeof(CorrectionState), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(c0, h->scalars.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
             MGX_TRY(check_device_error(h, true));                 // (nothing of the run has been handed out yet)
             if (!h->requeued) break;
+        }
+        if (profile) {
+            st_r->peak = hd_r->peak;
+            st_r->amplitude_c = hd_r->amplitude_coefficient;
+            st_r->average_rms = hd_r->average_rms;
+            st_r->match_rms = hd_r->match_rms;
+            st_r->divisions = hd_r->divisions;
+            st_r->loud_count = hd_r->loud_count;
+            st_r->piece = hd_r->piece;
         }
         std::memset(report, 0, sizeof(*report));
         report->final_amplitude_coefficient = st_r->amplitude_c;
@@ -1816,15 +1898,53 @@ extern "C" {
 int mgx_master(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
                int64_t n_reference, const mgx_config* cfg, float* result_dev, float* result_no_limiter_dev,
                float* result_no_limiter_normalized_dev, mgx_report* report) {
-    return master_impl(h, target_dev, n_target, reference_dev, n_reference, cfg, nullptr, result_dev,
+    return master_impl(h, target_dev, n_target, reference_dev, n_reference, nullptr, cfg, nullptr, result_dev,
                        result_no_limiter_dev, result_no_limiter_normalized_dev, report);
 }
 int mgx_master_with_fir(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
                         int64_t n_reference, const mgx_config* cfg, const float* fir_dev, float* result_dev,
                         float* result_no_limiter_dev, float* result_no_limiter_normalized_dev, mgx_report* report) {
     if (!fir_dev) return fail(MGX_ERR_ARGUMENT, "null FIR");
-    return master_impl(h, target_dev, n_target, reference_dev, n_reference, cfg, fir_dev, result_dev,
+    return master_impl(h, target_dev, n_target, reference_dev, n_reference, nullptr, cfg, fir_dev, result_dev,
                        result_no_limiter_dev, result_no_limiter_normalized_dev, report);
+}
+
+// ---- reference profiles -------------------------------------------------------
+int mgx_profile_bytes(const mgx_config* cfg, size_t* bytes) {
+    if (!cfg || !bytes) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (ilog2_exact(cfg->fft_size) < 0 || cfg->fft_size < 8 || cfg->fft_size > 65536)
+        return fail(MGX_ERR_ARGUMENT, "fft_size must be a power of two in [8, 65536]");
+    *bytes = sizeof(mgx_profile_header) + (size_t)2 * (cfg->fft_size / 2 + 1) * sizeof(double);
+    return 0;
+}
+
+int mgx_reference_profile(mgx_handle* h, const float* reference_dev, int64_t n_reference, const mgx_config* cfg,
+                          void* profile_dev) {
+    if (!h || !reference_dev || !profile_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(check_config(cfg));
+    HIP_TRY(hipSetDevice(h->device));
+    // mgx_analyze(is_reference = 1)'s chain, then the pack
+    TrackWork& w = h->track[1];
+    w.is_reference = 1;
+    MGX_TRY(run_analysis(h, cfg, reference_dev, n_reference, w));
+    MGX_TRY(run_levels(h, cfg, &w, nullptr));
+    const int bins = cfg->fft_size / 2 + 1;
+    hipLaunchKernelGGL(k_finish_spectra, dim3((2 * bins + 255) / 256), dim3(256), 0, h->stream, (const double*)w.part.p,
+                       (const TrackStats*)w.stats.p, w.segs_per_piece, cfg->fft_size, (double*)w.avg.p);
+    hipLaunchKernelGGL(k_profile_pack, dim3((2 * bins + 255) / 256), dim3(256), 0, h->stream, (const TrackStats*)w.stats.p,
+                       (const double*)w.avg.p, profile_want(cfg), (long long)n_reference, bins,
+                       (mgx_profile_header*)profile_dev, h->error_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mgx_master_with_profile(mgx_handle* h, const float* target_dev, int64_t n_target, const void* profile_dev,
+                            const mgx_config* cfg, const float* fir_dev, float* result_dev,
+                            float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
+                            mgx_report* report) {
+    if (!profile_dev) return fail(MGX_ERR_ARGUMENT, "null profile");
+    return master_impl(h, target_dev, n_target, nullptr, 0, (const mgx_profile_header*)profile_dev, cfg, fir_dev,
+                       result_dev, result_no_limiter_dev, result_no_limiter_normalized_dev, report);
 }
 
 int mgx_stage_timing(mgx_handle* h, int32_t enable) {

@@ -152,9 +152,11 @@ __device__ __forceinline__ int opaque(int v) {
 // audio is wrong and the call fails.  An expired wait of k_correction_tail means its workgroups were not resident
 // together (another process's kernels held the compute units): the host then runs the rounds again as one launch
 // each, which wait for nobody (mgx.hip, check_device_error).  DEVICE_ERROR_INPUT is not a wait at all: the level
-// analysis met a NaN or an infinity (k_match_curve), where the reference raises.
-constexpr int DEVICE_ERROR_LOOKBACK = 1, DEVICE_ERROR_TAIL = 2, DEVICE_ERROR_INPUT = 4;
-constexpr int DEVICE_ERROR_SLOT_LOOKBACK = 0, DEVICE_ERROR_SLOT_TAIL = 1, DEVICE_ERROR_SLOT_INPUT = 2, DEVICE_ERROR_SLOTS = 3;
+// analysis met a NaN or an infinity (k_match_curve), where the reference raises.  Nor is DEVICE_ERROR_PROFILE: a reference
+// profile whose header does not fit the call's Config (profile_kernels.h); its word holds WHICH field, not a 1.
+constexpr int DEVICE_ERROR_LOOKBACK = 1, DEVICE_ERROR_TAIL = 2, DEVICE_ERROR_INPUT = 4, DEVICE_ERROR_PROFILE = 8;
+constexpr int DEVICE_ERROR_SLOT_LOOKBACK = 0, DEVICE_ERROR_SLOT_TAIL = 1, DEVICE_ERROR_SLOT_INPUT = 2, DEVICE_ERROR_SLOT_PROFILE = 3,
+              DEVICE_ERROR_SLOTS = 4;
 
 // ---------------------------------------------------------------------------
 // code warming

@@ -449,17 +449,44 @@ class Device:
         return {name: (float(v) if v >= 0 else None) for name, v in zip(_native.STAGES, ms)}
 
     # ---- the boundary ------------------------------------------------------------
+    def reference_profile(self, reference, n_reference, native_config):
+        """``mgx_reference_profile`` on a reference in HBM (a DeviceBuffer): the profile's bytes
+        (``mgx_profile_header`` + spectra), downloaded.  ``profile.ReferenceProfile`` wraps them."""
+        lib = library()
+        nbytes = ctypes.c_size_t()
+        check(lib.mgx_profile_bytes(ctypes.byref(native_config), ctypes.byref(nbytes)))
+        with self.lock:
+            block = DeviceBuffer(self, nbytes.value)
+            try:
+                check(lib.mgx_reference_profile(self.handle, ctypes.c_void_p(reference.ptr), int(n_reference),
+                                                ctypes.byref(native_config), ctypes.c_void_p(block.ptr)))
+                host = ctypes.create_string_buffer(nbytes.value)
+                # (the blocking copy: a NaN or an infinity in the reference fails here)
+                check(lib.mgx_memcpy_d2h(self.handle, host, ctypes.c_void_p(block.ptr), nbytes.value))
+                self._keep_until_sync.clear()
+                return host.raw
+            finally:
+                block.release()
+
     def master(self, target, n_target, reference, n_reference, native_config, result=None,
-               result_no_limiter=None, result_no_limiter_normalized=None, want_report=True, fir=None):
+               result_no_limiter=None, result_no_limiter_normalized=None, want_report=True, fir=None, profile=None):
         """``mgx_master`` on device buffers.  Outputs are DeviceBuffers or None.  ``fir`` (a DeviceBuffer
-        holding [2][fft_size] float32) replaces the designed matching FIR: ``mgx_master_with_fir``."""
+        holding [2][fft_size] float32) replaces the designed matching FIR: ``mgx_master_with_fir``.  ``profile``
+        (a DeviceBuffer holding a reference profile) stands for the reference, which is then None:
+        ``mgx_master_with_profile``."""
         report = MgxReport() if want_report else None
 
         def p(b):
             return ctypes.c_void_p(b.ptr) if b is not None else None
 
         rep = ctypes.byref(report) if report is not None else None
-        if fir is None:
+        if profile is not None:
+            if reference is not None:
+                raise ValueError("master: a reference track or a reference profile, not both")
+            check(library().mgx_master_with_profile(
+                self.handle, p(target), n_target, p(profile), ctypes.byref(native_config), p(fir),
+                p(result), p(result_no_limiter), p(result_no_limiter_normalized), rep))
+        elif fir is None:
             check(library().mgx_master(
                 self.handle, p(target), n_target, p(reference), n_reference, ctypes.byref(native_config),
                 p(result), p(result_no_limiter), p(result_no_limiter_normalized), rep))

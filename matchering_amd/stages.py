@@ -38,6 +38,12 @@ def _as_frames(array, name):
     return np.ascontiguousarray(array, dtype=np.float32)
 
 
+def _is_profile(reference):
+    from .profile import ReferenceProfile
+
+    return isinstance(reference, ReferenceProfile)
+
+
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
          encodings=None, preview=None):
@@ -48,11 +54,19 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # or uint8 (n, 6) for packed 24-bit.  All additions to the reference's signature, keyword-only in
     # spirit.  ``target`` / ``reference`` may be int16 or int32 PCM as read from a file.  ``preview``: a
     # preview.PreviewRequest -- the A/B previews of preview_creator.py:30-94 are cut from the first requested
-    # output and from the target while both are still in HBM, and left in the request.)
+    # output and from the target while both are still in HBM, and left in the request.  ``reference`` may be a
+    # profile.ReferenceProfile: the reference's analysis results without its audio, made with this Config --
+    # mgx_master_with_profile; stage 1 then runs on the target alone.)
     dev = device if device is not None else default_device()
     target = _as_frames(target, "target")
-    reference = _as_frames(reference, "reference")
-    n, nr = target.shape[0], reference.shape[0]
+    profile = reference if _is_profile(reference) else None
+    if profile is not None:
+        profile.matches(config)                              # (ValueError before anything reaches the GPU)
+        reference, nr = None, 0
+    else:
+        reference = _as_frames(reference, "reference")
+        nr = reference.shape[0]
+    n = target.shape[0]
     native = config.to_native()
 
     debug_line()
@@ -61,11 +75,15 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
           f"({config.max_piece_size / config.internal_sample_rate:.2f} s) each")
     with dev.lock:
         t_dev = target.buf if isinstance(target, DeviceFrames) else dev.upload_frames(target)
-        r_dev = reference.buf if isinstance(reference, DeviceFrames) else dev.upload_frames(reference)
+        if profile is not None:
+            r_dev, p_dev = None, profile.resident(dev)       # (the profile's own buffer: kept, not released here)
+        else:
+            r_dev, p_dev = (reference.buf if isinstance(reference, DeviceFrames) else dev.upload_frames(reference)), None
         outs = [dev.alloc(n * 8) if need else None
                 for need in (need_default, need_no_limiter, need_no_limiter_normalized)]
         try:
-            report = dev.master(t_dev, n, r_dev, nr, native, *outs, fir=fir)
+            route = {} if p_dev is None else {"profile": p_dev}
+            report = dev.master(t_dev, n, r_dev, nr, native, *outs, fir=fir, **route)
             debug(f"target: {report.target_divisions} pieces of {report.target_piece} frames, "
                   f"{report.target_loud_count} of them loud; reference: {report.reference_divisions} pieces of "
                   f"{report.reference_piece} frames, {report.reference_loud_count} loud")
