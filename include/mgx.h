@@ -270,6 +270,30 @@ int mgx_master_with_profile(mgx_handle* h, const float* target_dev, int64_t n_ta
                             const mgx_config* cfg, const float* fir_dev, float* result_dev,
                             float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
                             mgx_report* report);
+/* Reference sets: several profiles pooled into one, "master this to the sound of these five records".  Every source
+ * stays what mgx_reference_profile made of its own track (normalised, cut and selected on its own); the merged profile
+ * is the reference's own means over the UNION of the sources' loud pieces, the piece as the unit: match_levels.py:62-71
+ * (get_average_rms over the loud pieces' RMS) and match_frequencies.py:30-42 (the mean over pieces and segments).  With
+ * w_i = weights[i] ("count this reference w times"), n_i = w_i * loud_count_i and N = sum n_i, float64 sums in source
+ * order:
+ *     spectra[k]            = sum_i n_i * spectra_i[k] / N
+ *     match_rms             = sqrt(sum_i n_i * match_rms_i^2 / N)
+ *     amplitude_coefficient = max_i amplitude_coefficient_i      (match_levels.py:29-44 on the largest peak)
+ *     peak                  = max_i peak_i
+ *     loud_count = N,  divisions = sum_i w_i * divisions_i,  frames = sum_i w_i * frames_i
+ *     average_rms           = sqrt(sum_i w_i divisions_i average_rms_i^2 / divisions)     (informational)
+ *     piece                 = the sources' common value, or 0 when they differ
+ * The result is an ordinary version-1 profile of mgx_profile_bytes(cfg) bytes: mgx_master_with_profile takes it, and so
+ * does a later merge.  One source with weight 1 comes out byte for byte.  profiles_dev: a HOST array of `count` device
+ * pointers; weights: a host array, or NULL for all 1.  Only queued on the handle's stream: the call waits for nothing.
+ * MGX_ERR_ARGUMENT at once: a null argument, count outside [1, MGX_PROFILE_MERGE_MAX], a weight outside [1, 65536],
+ * profile_dev overlapping a source.  A source that does not fit `cfg` (as for mgx_master_with_profile), whose
+ * loud_count is not positive or exceeds its divisions, or counts whose weighted sums leave int32: the device finds
+ * out, writes an output whose magic is 0, and the next blocking call fails with MGX_ERR_ARGUMENT naming the field and
+ * the source. */
+#define MGX_PROFILE_MERGE_MAX 64
+int mgx_profile_merge(mgx_handle* h, const void* const* profiles_dev, const int32_t* weights, int32_t count,
+                      const mgx_config* cfg, void* profile_dev);
 
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of

@@ -89,6 +89,7 @@ class MgxProfileHeader(ctypes.Structure):
 
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
+PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
 
 
 # every symbol include/mgx.h declares: name -> (restype, argtypes)
@@ -116,6 +117,7 @@ SYMBOLS = {
     "mgx_reference_profile": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxConfig), _VP]),
     "mgx_master_with_profile": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, ctypes.POINTER(MgxConfig), _VP,
                                                _VP, _VP, _VP, ctypes.POINTER(MgxReport)]),
+    "mgx_profile_merge": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), c_int32_p, ctypes.c_int32, ctypes.POINTER(MgxConfig), _VP]),
     "mgx_analyze": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxConfig), ctypes.c_int,
                                    c_double_p, c_double_p, c_double_p, c_int32_p, c_int64_p,
                                    c_double_p, c_int32_p, c_double_p, c_double_p]),

@@ -28,7 +28,8 @@ and on a node with 8 GPUs::
 
 ``jobs.json`` is a list of ``{"target": path, "reference": path, "results": [{"file": path,
 "subtype": "PCM_16", "use_limiter": true, "normalize": true}, ...]}``; in place of ``"reference"`` a job may name a
-``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py).
+``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
+list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).
 """
 
 import json
@@ -356,6 +357,37 @@ class _SharedReference:
             return os.path.abspath(self.path)
 
 
+class _ReferenceSet:
+    """A job's "references": left to the lane that masters the job, which makes a profile of every element
+    (``_analyze_reference`` for an audio file) and merges them (``ReferenceProfile.merge``)."""
+
+    def __init__(self, items):
+        self.items = list(items)
+
+    @property
+    def key(self):
+        """What tells two sets apart: the elements in order (the order of a merge's float64 sums)."""
+        return tuple(("object", id(item)) if _is_profile_object(item) else ("file", _SharedReference(item).key)
+                     for item in self.items)
+
+
+def _is_profile_object(item):
+    from .profile import ReferenceProfile
+
+    return isinstance(item, ReferenceProfile)
+
+
+def _audio_files(job):
+    """The audio files a job names as its reference, alone or in a set (saved profiles are not among them)."""
+    from .profile import is_profile_file
+
+    if job.get("references") is not None:
+        return [item for item in job["references"] if not _is_profile_object(item) and not is_profile_file(item)]
+    if job.get("reference") is not None and job.get("reference_profile") is None:
+        return [job["reference"]]
+    return []
+
+
 def _analyze_reference(path, config, device):
     from .profile import ReferenceProfile
 
@@ -439,9 +471,9 @@ def _needs_of(results):
 def _load_job(job, config, gpu=False, shared=False):
     """Load + check both files of a job (core.py:52-74), on a host thread.  Returns (target, reference,
     later): with ``later`` (a ``_Later``) a track is still as its file holds it and goes to the GPU that way.  A job
-    with a "reference_profile", or whose reference file is ``shared`` with other jobs (``process_batch``'s
-    ``share_references``), loads its target only: ``reference`` is then the ``ReferenceProfile`` / a
-    ``_SharedReference``, and the equality check of checker.py:140-142, which needs the reference's audio, is not made.  The
+    with a "reference_profile" or "references", or whose reference file is ``shared`` with other jobs
+    (``process_batch``'s ``share_references``), loads its target only: ``reference`` is then the ``ReferenceProfile`` / a
+    ``_ReferenceSet`` / a ``_SharedReference``, and the equality check of checker.py:140-142, which needs the reference's audio, is not made.  The
     target's peak statistics (checker.py:118-130) are then left to the lane that masters it (``mgx_peak_count``),
     and with ``gpu`` so is the conversion of a mono or off-rate track (``device.takes_resident``, the rule
     ``core.process`` uses): a loader thread never spends seconds in the host resampler while its lane idles."""
@@ -470,7 +502,8 @@ def _load_job(job, config, gpu=False, shared=False):
     convert_t = deferred and _changes(target, rate_t, internal)
     target, rate_t = check(target, rate_t, config, "target", peaks=LATER if deferred else None, on_device=convert_t)
     profile = _job_profile(job)
-    if profile is not None or shared:
+    several = _ReferenceSet(job["references"]) if job.get("references") is not None else None
+    if profile is not None or several is not None or shared:
         if profile is not None:
             profile.matches(config)
         frames_t = frames_t if convert_t else target.shape[0]
@@ -480,7 +513,7 @@ def _load_job(job, config, gpu=False, shared=False):
             from .core import NO_EQUALITY_CHECK
 
             debug(NO_EQUALITY_CHECK)
-        stand_in = profile if profile is not None else _SharedReference(job["reference"])
+        stand_in = profile if profile is not None else (several if several is not None else _SharedReference(job["reference"]))
         return target, stand_in, (_Later(file_rate_t, None, False) if deferred else None)
     reference, rate_r = load(job["reference"], "reference", temp_folder, pcm=True)
     file_rate_r = rate_r
@@ -519,9 +552,11 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     """``process`` for a list of jobs, this rank's share only.
 
     ``jobs``: dicts with "target", "reference" (paths) and "results" (list of ``Result``); in place of "reference" a
-    job may name a "reference_profile" (a ``ReferenceProfile`` or the path of a saved one).  With
-    ``share_references=True`` the jobs of this rank that name the same reference FILE (``os.path.samefile``) have it
-    loaded and analysed once per lane device and are mastered against that profile.  Off by default: the profile
+    job may name a "reference_profile" (a ``ReferenceProfile`` or the path of a saved one) or "references" (a list of
+    audio files, saved profiles and ``ReferenceProfile``s, merged into one profile on the lane that masters the job).
+    With ``share_references=True`` the jobs of this rank that name the same reference FILE (``os.path.samefile``), alone
+    or in a set, have it loaded and analysed once per lane device and are mastered against that profile, and every
+    distinct set is merged once per lane.  Off by default: the profile
     route agrees with the pair route to the project's tolerances, not bit for bit.  Returns
     the indices of the jobs this rank mastered.  The first failing job aborts the rank's batch and
     its exception is re-raised (after the jobs already in flight have finished)."""
@@ -537,8 +572,7 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     if share_references:
         seen = {}
         for i in mine:
-            if jobs[i].get("reference") is not None and jobs[i].get("reference_profile") is None:
-                key = _SharedReference(jobs[i]["reference"]).key
+            for key in {_SharedReference(path).key for path in _audio_files(jobs[i])}:
                 seen[key] = seen.get(key, 0) + 1
         shared_keys = {key for key, count in seen.items() if count > 1}
 
@@ -550,14 +584,42 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
         def worker_for(lane):
             workers = {}
             profiles = {}                              # share_references: reference file -> its profile on this lane
+            merged = {}                                # ... and set of references -> its merged profile
+
+            def analysed(path, kept):
+                key = _SharedReference(path).key
+                if key not in kept:
+                    kept[key] = _analyze_reference(
+                        path, config, None if master is not None else lane_device(device_index, lane))
+                return kept[key]
+
+            def merged_set(several):
+                """One profile per element -- with share_references the lane's own of a file it has analysed before --
+                and their merge."""
+                from .profile import ReferenceProfile, is_profile_file
+
+                kept = profiles if share_references else {}
+                sources = []
+                for element in several.items:
+                    if _is_profile_object(element) or is_profile_file(element):
+                        profile = element if _is_profile_object(element) else ReferenceProfile.load(element)
+                        profile.matches(config)
+                        sources.append(profile)
+                    else:
+                        sources.append(analysed(element, kept))
+                return ReferenceProfile.merge(sources, device=None if master is not None else lane_device(device_index, lane))
 
             def run(item):
                 index, (target, reference, later) = item
                 if isinstance(reference, _SharedReference):
-                    if reference.key not in profiles:
-                        profiles[reference.key] = _analyze_reference(
-                            reference.path, config, None if master is not None else lane_device(device_index, lane))
-                    reference = profiles[reference.key]
+                    reference = analysed(reference.path, profiles)
+                elif isinstance(reference, _ReferenceSet):
+                    if not share_references:
+                        reference = merged_set(reference)
+                    else:
+                        if reference.key not in merged:
+                            merged[reference.key] = merged_set(reference)
+                        reference = merged[reference.key]
                 needs = _needs_of(jobs[index]["results"])
                 key = (needs, _wanted_encodings(jobs[index]["results"]))
                 if key not in workers:
@@ -615,7 +677,7 @@ def jobs_from_json(path):
         results = [Result(r["file"], subtype=r.get("subtype", "PCM_16"), use_limiter=r.get("use_limiter", True),
                           normalize=r.get("normalize", True)) for r in item["results"]]
         job = {"target": item["target"], "results": results}
-        for key in ("reference", "reference_profile"):
+        for key in REFERENCE_KEYS:
             if item.get(key) is not None:
                 job[key] = item[key]
         _job_reference_keys(job)
@@ -623,12 +685,19 @@ def jobs_from_json(path):
     return jobs
 
 
+REFERENCE_KEYS = ("reference", "reference_profile", "references")
+
+
 def _job_reference_keys(job):
-    """A job names its reference exactly once: "reference" (an audio file) or "reference_profile" (a saved profile)."""
-    named = [key for key in ("reference", "reference_profile") if job.get(key) is not None]
+    """A job names its reference exactly once: "reference" (an audio file), "reference_profile" (a saved profile) or
+    "references" (a list of audio files and saved profiles, merged into one profile)."""
+    named = [key for key in REFERENCE_KEYS if job.get(key) is not None]
     if len(named) != 1:
-        raise ValueError(f'job for {job.get("target")!r}: exactly one of "reference" and "reference_profile" is needed, '
-                         f'got {named or "neither"}')
+        raise ValueError(f'job for {job.get("target")!r}: exactly one of "reference", "reference_profile" and "references" '
+                         f'is needed, got {named or "none of them"}')
+    several = job.get("references")
+    if several is not None and (not isinstance(several, (list, tuple)) or not several):
+        raise ValueError(f'job for {job.get("target")!r}: "references" is a list of at least one file, got {several!r}')
 
 
 def main(argv=None):

@@ -122,13 +122,17 @@ def _read_pair(target_path, reference_path, config, temp_folder):
     return target, reference, resident
 
 
-def _as_profile(reference):
-    """The ``ReferenceProfile`` that ``process`` was given in the reference's place -- the object itself, or the path of
-    a saved one, recognised by the file's magic and not by its name -- or None for an audio file."""
-    from .profile import ReferenceProfile, is_profile_file
+def _as_profile(reference, config=None):
+    """The ``ReferenceProfile`` that ``process`` was given in the reference's place -- the object itself, the path of
+    a saved one, recognised by the file's magic and not by its name, or a SET of references (``is_reference_set``: each
+    file loaded and analysed as ``process`` does with its reference, same log codes, and the lot merged into one
+    profile) -- or None for an audio file."""
+    from .profile import ReferenceProfile, is_profile_file, is_reference_set
 
     if isinstance(reference, ReferenceProfile):
         return reference
+    if is_reference_set(reference):
+        return ReferenceProfile.analyze(reference, config)
     if isinstance(reference, (str, bytes, os.PathLike)) and is_profile_file(reference):
         return ReferenceProfile.load(reference)
     return None
@@ -191,9 +195,9 @@ def process(target: str, reference: str, results: list, config: Config = None,
         raise RuntimeError("The result list is empty")
     temp_folder = config.temp_folder or get_temp_folder(results)
 
-    profile = _as_profile(reference)
+    profile = _as_profile(reference, config)
     if profile is not None:
-        # the reference is a profile: only the target is loaded and checked
+        # the reference is a profile (given, or just made of a set of references): only the target is loaded and checked
         profile.matches(config)
         target_audio, frames = read_track(target, "target", config, temp_folder, _gpu())
         reference_audio, resident = profile, [frames, profile]

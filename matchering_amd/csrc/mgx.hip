@@ -1185,12 +1185,18 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (what & DEVICE_ERROR_PROFILE) {
         // (before the input report: a profile that was not read makes no statement about anybody's samples)
+        // (k_profile_merge: the verdict in the low byte, the refused source's position + 1 above it)
         static const char* const FIELDS[] = {"", "magic", "version", "internal_sample_rate", "fft_size", "max_piece_size",
-                                             "threshold", "min_value"};
-        const char* field = profile_field > 0 && profile_field < 8 ? FIELDS[profile_field] : "header";
-        return fail(MGX_ERR_ARGUMENT, std::string("the reference profile does not fit this call: its ") + field +
-                                      (profile_field <= PROFILE_BAD_VERSION
+                                             "threshold", "min_value", "loud_count"};
+        const int verdict = profile_field & 0xff, source = profile_field >> 8;
+        const char* field = verdict > 0 && verdict < 9 ? FIELDS[verdict] : "header";
+        const std::string whose = source > 0 ? "the reference profile, source " + std::to_string(source - 1) + " of the merge,"
+                                             : "the reference profile";
+        return fail(MGX_ERR_ARGUMENT, whose + " does not fit this call: its " + field +
+                                      (verdict <= PROFILE_BAD_VERSION
                                            ? " is not that of a profile this library writes (mgx_profile_header)"
+                                       : verdict == PROFILE_BAD_COUNT
+                                           ? " is not positive or exceeds its divisions, or the merged counts do not fit 32 bits"
                                            : " differs from the Config's; a profile is used with the Config it was made with") +
                                       "; the outputs of the calls since the last synchronisation are not valid");
     }
@@ -1242,7 +1248,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
 // ---------------------------------------------------------------------------
 extern "C" {
 
-int mgx_version(void) { return 102; }
+int mgx_version(void) { return 103; }
 const char* mgx_last_error(void) { return g_error.c_str(); }
 
 int mgx_device_count(int* count) {
@@ -1945,6 +1951,37 @@ int mgx_master_with_profile(mgx_handle* h, const float* target_dev, int64_t n_ta
     if (!profile_dev) return fail(MGX_ERR_ARGUMENT, "null profile");
     return master_impl(h, target_dev, n_target, nullptr, 0, (const mgx_profile_header*)profile_dev, cfg, fir_dev,
                        result_dev, result_no_limiter_dev, result_no_limiter_normalized_dev, report);
+}
+
+int mgx_profile_merge(mgx_handle* h, const void* const* profiles_dev, const int32_t* weights, int32_t count,
+                      const mgx_config* cfg, void* profile_dev) {
+    if (!h || !profiles_dev || !cfg || !profile_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (count < 1 || count > MGX_PROFILE_MERGE_MAX)
+        return fail(MGX_ERR_ARGUMENT, "mgx_profile_merge takes 1 to " + std::to_string(MGX_PROFILE_MERGE_MAX) + " profiles, got " +
+                                      std::to_string(count) + ": merge in groups, a merged profile is a source like any other");
+    size_t bytes = 0;
+    MGX_TRY(mgx_profile_bytes(cfg, &bytes));
+    ProfileMergeArgs a = {};
+    a.count = count;
+    const uintptr_t out = (uintptr_t)profile_dev;
+    for (int i = 0; i < count; ++i) {
+        const int32_t w = weights ? weights[i] : 1;
+        if (!profiles_dev[i]) return fail(MGX_ERR_ARGUMENT, "null profile at position " + std::to_string(i));
+        if (w < 1 || w > 65536)
+            return fail(MGX_ERR_ARGUMENT, "weight " + std::to_string(w) + " at position " + std::to_string(i) + " is outside [1, 65536]");
+        const uintptr_t src = (uintptr_t)profiles_dev[i];
+        if (src < out + bytes && out < src + bytes)
+            return fail(MGX_ERR_ARGUMENT, "profile_dev overlaps the source at position " + std::to_string(i) +
+                                          ": the merged profile needs a block of its own");
+        a.src[i] = (const mgx_profile_header*)profiles_dev[i];
+        a.weight[i] = w;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const int bins = cfg->fft_size / 2 + 1;
+    hipLaunchKernelGGL(k_profile_merge, dim3((2 * bins + 255) / 256), dim3(256), 0, h->stream, a, profile_want(cfg), bins,
+                       (mgx_profile_header*)profile_dev, h->error_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int mgx_stage_timing(mgx_handle* h, int32_t enable) {

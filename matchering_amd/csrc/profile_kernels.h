@@ -2,7 +2,8 @@
 // a block of memory instead of recomputed per target.  Device only:
 //   * k_profile_pack: TrackStats + finished loud-piece spectra of a reference -> a profile (mgx_reference_profile),
 //   * k_profile_curve: k_match_curve (fir_kernels.h) for a target ALONE, the reference's terms read from a profile,
-//   * k_profile_raw: k_fir_raw's sibling behind k_levels + k_average_spectra, for piece tables beyond a workgroup's LDS.
+//   * k_profile_raw: k_fir_raw's sibling behind k_levels + k_average_spectra, for piece tables beyond a workgroup's LDS,
+//   * k_profile_merge: several profiles pooled into one over the union of their loud pieces (mgx_profile_merge).
 #pragma once
 
 #include "../../include/mgx.h"
@@ -19,7 +20,7 @@ struct ProfileWant {
 };
 // What the host reads in the handle's error word DEVICE_ERROR_SLOT_PROFILE: the first header field that does not fit.
 enum { PROFILE_OK = 0, PROFILE_BAD_MAGIC, PROFILE_BAD_VERSION, PROFILE_BAD_RATE, PROFILE_BAD_FFT, PROFILE_BAD_PIECE,
-       PROFILE_BAD_THRESHOLD, PROFILE_BAD_MIN_VALUE };
+       PROFILE_BAD_THRESHOLD, PROFILE_BAD_MIN_VALUE, PROFILE_BAD_COUNT };
 // (every thread reads the same few header words: the block behind the header is only as long as the profile's OWN
 // fft_size makes it, so nobody may touch the spectra before this has answered PROFILE_OK)
 __device__ __forceinline__ int profile_check(const mgx_profile_header* p, const ProfileWant& want) {
@@ -234,6 +235,90 @@ __global__ __launch_bounds__(256) void k_profile_raw(FirPlanView pl, const doubl
     // (a refused profile: its spectra are not read and the curve is flat, as in k_profile_curve)
     const double ar = verdict == PROFILE_OK ? profile_spectra(prof)[(size_t)plane * pl.bins + k] : 0.0;
     raw[(size_t)plane * pl.bins + k] = verdict == PROFILE_OK ? ar / fmax(pl.min_value, at) : 1.0;
+}
+
+// The sources of a merge, by value in the kernel's arguments (64 x 12 bytes): one launch, nothing copied.
+struct ProfileMergeArgs {
+    const mgx_profile_header* src[MGX_PROFILE_MERGE_MAX];
+    int weight[MGX_PROFILE_MERGE_MAX];      // positive: "count this reference w times"
+    int count;
+};
+// Several profiles into one: the reference's own means (match_levels.py:62-71 get_average_rms over the loud pieces'
+// RMS, match_frequencies.py:30-42 the mean over pieces and segments) over the UNION of the sources' loud-piece lists,
+// source i counted weight[i] times.  With n_i = weight[i] * loud_count_i and N = sum n_i:
+//     spectra[k] = sum_i n_i avg_i[k] / N,   match_rms = sqrt(sum_i n_i match_i^2 / N),   peak and coefficient: the largest
+// -- float64 sums in source order.  Grid over 2 * bins values, 256 threads; thread 0 of workgroup 0 writes the header.
+// Every thread checks every source's header first (profile_check, and counts that are positive and fit int32 when
+// summed): a source's spectra are only as long as its OWN fft_size makes them.  The first refused source leaves
+// verdict | (index + 1) << 8 in the error word and an output header whose magic is 0; no spectra are read then.
+__global__ __launch_bounds__(256) void k_profile_merge(ProfileMergeArgs a, ProfileWant want, int bins,
+                                                       mgx_profile_header* out, int* error) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int refused = 0;
+    long long loud = 0, divisions = 0;
+    for (int s = 0; s < a.count; ++s) {
+        const mgx_profile_header* p = a.src[s];
+        int verdict = profile_check(p, want);
+        if (verdict == PROFILE_OK) {
+            const long long w = a.weight[s];
+            if (p->loud_count <= 0 || p->divisions < p->loud_count) verdict = PROFILE_BAD_COUNT;
+            loud += w * p->loud_count;
+            divisions += w * p->divisions;
+            if (loud > 0x7fffffffll || divisions > 0x7fffffffll) verdict = PROFILE_BAD_COUNT;
+        }
+        if (verdict != PROFILE_OK) {
+            refused = verdict | (s + 1) << 8;
+            break;
+        }
+    }
+    if (refused) {
+        if (i == 0) {
+            mgx_profile_header hd = {};                         // (magic 0: never a usable profile)
+            *out = hd;
+            if (error) error[DEVICE_ERROR_SLOT_PROFILE] = refused;
+        }
+        return;
+    }
+    // one source counted once is that source: its bytes as they are ((n x) / n is not always x)
+    const bool copy = a.count == 1 && a.weight[0] == 1;
+    const double total = (double)loud;
+    if (i < 2 * bins) {
+        double sum = 0.0;
+        for (int s = 0; s < a.count; ++s) {
+            const mgx_profile_header* p = a.src[s];
+            const double n = (double)((long long)a.weight[s] * p->loud_count);
+            sum += n * profile_spectra(p)[i];
+        }
+        reinterpret_cast<double*>(out + 1)[i] = copy ? profile_spectra(a.src[0])[i] : sum / total;
+    }
+    if (i != 0) return;
+    if (copy) {
+        *out = *a.src[0];
+    } else {
+        mgx_profile_header hd = *a.src[0];                      // magic, version and the five Config fields
+        hd.frames = 0;
+        double match = 0.0, average = 0.0;
+        for (int s = 0; s < a.count; ++s) {
+            const mgx_profile_header* p = a.src[s];
+            const long long w = a.weight[s];
+            hd.frames += w * p->frames;
+            if (p->piece != hd.piece) hd.piece = 0;
+            hd.peak = fmax(hd.peak, p->peak);
+            hd.amplitude_coefficient = fmax(hd.amplitude_coefficient, p->amplitude_coefficient);   // match_levels.py:29-44 on the largest peak
+            match += (double)(w * p->loud_count) * (p->match_rms * p->match_rms);
+            average += (double)(w * p->divisions) * (p->average_rms * p->average_rms);
+        }
+        hd.divisions = (int)divisions;
+        hd.loud_count = (int)loud;
+        hd.match_rms = sqrt(match / total);
+        hd.average_rms = sqrt(average / (double)divisions);
+        *out = hd;
+    }
+    if (!error) return;
+    for (int s = 0; s < a.count; ++s) {                          // (k_profile_pack's report, for a source that carries one)
+        const mgx_profile_header* p = a.src[s];
+        if (!(fabs(p->match_rms) < 1.0e300) || !(fabs(p->amplitude_coefficient) < 1.0e300)) error[DEVICE_ERROR_SLOT_INPUT] = 1;
+    }
 }
 
 }  // namespace mgx

@@ -468,6 +468,27 @@ class Device:
             finally:
                 block.release()
 
+    def profile_merge(self, sources, weights, native_config):
+        """``mgx_profile_merge`` on profiles in HBM (DeviceBuffers, at most 64): the merged profile's bytes, downloaded.
+        One launch and one copy; a source that does not fit fails at the copy, naming its field and position."""
+        lib = library()
+        nbytes = ctypes.c_size_t()
+        check(lib.mgx_profile_bytes(ctypes.byref(native_config), ctypes.byref(nbytes)))
+        count = len(sources)
+        pointers = (ctypes.c_void_p * count)(*[b.ptr for b in sources])
+        counted = (ctypes.c_int32 * count)(*weights)
+        with self.lock:
+            block = DeviceBuffer(self, nbytes.value)
+            try:
+                check(lib.mgx_profile_merge(self.handle, pointers, counted, count, ctypes.byref(native_config),
+                                            ctypes.c_void_p(block.ptr)))
+                host = ctypes.create_string_buffer(nbytes.value)
+                check(lib.mgx_memcpy_d2h(self.handle, host, ctypes.c_void_p(block.ptr), nbytes.value))
+                self._keep_until_sync.clear()
+                return host.raw
+            finally:
+                block.release()
+
     def master(self, target, n_target, reference, n_reference, native_config, result=None,
                result_no_limiter=None, result_no_limiter_normalized=None, want_report=True, fir=None, profile=None):
         """``mgx_master`` on device buffers.  Outputs are DeviceBuffers or None.  ``fir`` (a DeviceBuffer

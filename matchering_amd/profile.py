@@ -7,6 +7,10 @@ kilobytes, so that any number of targets are mastered against it without its aud
     profile.save("reference.mgxp")
     mg.process("target.wav", "reference.mgxp", [mg.pcm16("out.wav")], config)
 
+Several references make one profile too -- "master this to the sound of these five records": every source is analysed
+on its own as above, and ``ReferenceProfile.merge`` pools their loud pieces (``mgx_profile_merge``); a list or tuple
+in a reference's place (``analyze``, ``process``, a job's "references") means exactly that.
+
 The bytes are those of the device block (``mgx_profile_header`` + 2 x (fft_size / 2 + 1) float64, little-endian);
 a saved file puts eight bytes of its own magic in front.  A profile belongs to the ``Config`` fields its analysis
 depends on (``internal_sample_rate``, ``fft_size``, ``max_piece_size``, ``threshold``, ``min_value``): ``matches``
@@ -28,6 +32,7 @@ FILE_MAGIC = b"MGXPROF1"
 HEADER_BYTES = ctypes.sizeof(MgxProfileHeader)
 # (name in the header, name in Config): the fields a profile is tied to
 CONFIG_FIELDS = ("internal_sample_rate", "fft_size", "max_piece_size", "threshold", "min_value")
+MAX_WEIGHT = 65536          # of one source of a merge (include/mgx.h, mgx_profile_merge)
 
 
 def profile_bytes(config):
@@ -45,6 +50,18 @@ def is_profile_file(path):
             return fh.read(len(FILE_MAGIC)) == FILE_MAGIC
     except (OSError, TypeError, ValueError):
         return False
+
+
+def is_reference_set(reference):
+    """Whether ``reference`` names a SET of references: a list or tuple whose elements are paths (audio files or saved
+    profiles), ``ReferenceProfile``s, ``DeviceFrames`` or (n, channels) arrays.  Anything else -- nested lists of
+    numbers among them -- is what it was before there were sets: one track."""
+    from .device import DeviceFrames
+
+    if not isinstance(reference, (list, tuple)):
+        return False
+    return all(isinstance(item, (str, bytes, os.PathLike, ReferenceProfile, DeviceFrames))
+               or (isinstance(item, np.ndarray) and item.ndim == 2) for item in reference)
 
 
 class ReferenceProfile:
@@ -78,9 +95,22 @@ class ReferenceProfile:
     def analyze(cls, reference, config, device=None):
         """Analyse a reference: a path (loaded, checked and brought to the internal rate as ``process`` does with its
         reference, same log codes), an (n, 2) array (float, or integer PCM as a file holds it) or ``DeviceFrames``
-        (left alone, not released)."""
+        (left alone, not released).  A SET of references (``is_reference_set``: a list or tuple of any of these, of
+        ``ReferenceProfile``s and of saved profiles' paths) becomes one profile: each element is made into a profile as
+        above -- a profile must have been made with this Config, ``matches`` -- and the lot is merged (``merge``)."""
         from .device import DeviceFrames, default_device
 
+        if is_reference_set(reference):
+            profiles = []
+            for item in reference:
+                if isinstance(item, (str, bytes, os.PathLike)) and is_profile_file(item):
+                    item = cls.load(item)
+                if isinstance(item, ReferenceProfile):
+                    item.matches(config)
+                    profiles.append(item)
+                else:
+                    profiles.append(cls.analyze(item, config, device))
+            return cls.merge(profiles, device=device)
         dev = device if device is not None else default_device()
         if isinstance(reference, (str, bytes, os.PathLike)):
             frames = _load_reference(reference, config, dev)
@@ -100,6 +130,60 @@ class ReferenceProfile:
                 return cls(dev.reference_profile(buf, reference.shape[0], config.to_native()))
             finally:
                 buf.release()
+
+    @classmethod
+    def merge(cls, profiles, weights=None, device=None):
+        """One profile out of several: the reference's own means (match_levels.py:62-71, match_frequencies.py:30-42)
+        over the UNION of the sources' loud pieces -- every source stays what its own analysis made of it, so saved
+        profiles merge without anybody's audio.  ``weights``: positive integers up to 65536, "count this reference w
+        times" (default 1 each).  The sources must share the five Config fields a profile is tied to; the first that
+        differs from source 0 is a ``ValueError`` naming the field and its position, before anything reaches a device.
+        The result is an ordinary profile (include/mgx.h, ``mgx_profile_merge``, has the formulas) and may be merged
+        again; one source with weight 1 comes back byte for byte.  More than 64 sources are merged in groups of up to
+        64 and the group results merged again: that regroups the float64 sums, so the result may differ from a
+        single merge's in the last bits (the integer fields are the same)."""
+        profiles = list(profiles)
+        if not profiles:
+            raise ValueError("merge: the list of reference profiles is empty")
+        for i, item in enumerate(profiles):
+            if not isinstance(item, ReferenceProfile):
+                raise TypeError(f"merge: source {i} is {type(item).__name__}, not a ReferenceProfile")
+        weights = [1] * len(profiles) if weights is None else list(weights)
+        if len(weights) != len(profiles):
+            raise ValueError(f"merge: {len(profiles)} profiles but {len(weights)} weights")
+        for i, w in enumerate(weights):
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= w <= MAX_WEIGHT:
+                raise ValueError(f"merge: weight {w!r} of source {i} is not a positive integer up to {MAX_WEIGHT}")
+        weights = [int(w) for w in weights]
+        first = profiles[0]
+        for i, item in enumerate(profiles[1:], 1):
+            for name in CONFIG_FIELDS:
+                have, want = getattr(item._header, name), getattr(first._header, name)
+                if have != want:
+                    raise ValueError(f"merge: source {i} was made with {name} = {have!r}, source 0 with {name} = {want!r}: "
+                                     f"profiles merge only among those made with the same Config")
+        for name in ("loud_count", "divisions"):
+            if sum(w * getattr(item, name) for w, item in zip(weights, profiles)) > 2 ** 31 - 1:
+                raise ValueError(f"merge: the merged {name} does not fit the profile's 32-bit field")
+        from .device import default_device
+
+        dev = device if device is not None else default_device()
+        native = first._native_config()
+        with dev.lock:
+            while len(profiles) > _native.PROFILE_MERGE_MAX:
+                groups = range(0, len(profiles), _native.PROFILE_MERGE_MAX)
+                profiles = [cls(dev.profile_merge([p.resident(dev) for p in profiles[g:g + _native.PROFILE_MERGE_MAX]],
+                                                  weights[g:g + _native.PROFILE_MERGE_MAX], native)) for g in groups]
+                weights = [1] * len(profiles)
+            return cls(dev.profile_merge([p.resident(dev) for p in profiles], weights, native))
+
+    def _native_config(self):
+        """An ``mgx_config`` with the five fields this profile was made with (the others at their defaults)."""
+        native = _native.MgxConfig()
+        _native.check(_native.library().mgx_config_default(ctypes.byref(native)))
+        for name in CONFIG_FIELDS:
+            setattr(native, name, getattr(self._header, name))
+        return native
 
     # ---- files -----------------------------------------------------------------------------
     def save(self, path):
