@@ -295,6 +295,40 @@ int mgx_master_with_profile(mgx_handle* h, const float* target_dev, int64_t n_ta
 int mgx_profile_merge(mgx_handle* h, const void* const* profiles_dev, const int32_t* weights, int32_t count,
                       const mgx_config* cfg, void* profile_dev);
 
+/* Loudness metering on frames in HBM: ITU-R BS.1770-4 integrated loudness and true peak, EBU Tech 3341 momentary and
+ * short-term maxima, EBU Tech 3342 loudness range -- what a delivery specification states ("-14 LUFS, -1 dBTP") and
+ * neither mgx_report's RMS coefficients nor mgx_peak_count's sample peak can say (the reference has no meter at all; its
+ * limiter's ceiling, hyrax.py:78-99, is a sample-peak ceiling).  Part of the new surface, like the handle.
+ *   K-weighting: two float64 biquads per channel (high shelf, high-pass) from the closed form that gives BS.1770-4's
+ *     tables at 48 kHz, at any rate from 8000 Hz; transposed direct form II, zero state at frame 0.
+ *   sub-blocks: S = (sample_rate + 5) / 10 frames; sub_energy[s][c] = sum of the K-weighted squares of channel c over
+ *     sub-block s, s < n / S (the n % S frames behind the last sub-block count for the peaks only).
+ *   momentary / short-term blocks: 4 / 30 sub-blocks stepping one; l = -0.691 + 10 log10(mean square, both channels
+ *     weighted 1).  integrated: the momentary blocks above -70 LUFS and above (their loudness - 10).  range: short-term
+ *     blocks stepping ten, above -70 and above (their loudness - 20), 95th minus 10th percentile
+ *     (index int((m - 1) q + 0.5) of the sorted values).  Where no block qualifies (silence, fewer than 4 sub-blocks) the
+ *     loudness fields are -infinity, never NaN, and the range is 0.
+ *   true_peak: largest magnitude of the 4x oversampled track, oversampled by h[k] = sinc(k / 4) * kaiser(49, 8.0)[k + 24]
+ *     in float64, frames outside the track zero; sample_peak: the largest sample magnitude.  Both linear (1.0 = 0 dBFS).
+ * mgx_loudness: one launch that reads the frames once, waits for the result.  sub_energy (host, [capacity][2], may be
+ * NULL) receives the n / S sub-block energies and *count (may be NULL) their number.  n == 0 and n < S succeed.
+ * MGX_ERR_ARGUMENT: a null handle, report or (n > 0) x_dev, sample_rate < 8000, capacity < n / S, and a track with a NaN
+ * or an infinite sample (the handle is good for the next call).
+ * mgx_loudness_gate: the host half on its own -- the four loudness fields (and sub_blocks, sub_block_frames) from
+ * `count` sub-block energies; the peaks are left as they are.  Needs no GPU. */
+typedef struct mgx_loudness_report {
+    double integrated;                   /* LUFS */
+    double range;                        /* LU */
+    double momentary_max, short_term_max;/* LUFS */
+    double true_peak, sample_peak;       /* linear */
+    int64_t sub_blocks;
+    int32_t sub_block_frames;
+    int32_t reserved;
+} mgx_loudness_report;
+int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_rate, mgx_loudness_report* report,
+                 double* sub_energy, int64_t capacity, int64_t* count);
+int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_rate, mgx_loudness_report* report);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

@@ -87,6 +87,22 @@ class MgxProfileHeader(ctypes.Structure):
     ]
 
 
+class MgxLoudnessReport(ctypes.Structure):
+    """mgx_loudness_report (include/mgx.h)."""
+
+    _fields_ = [
+        ("integrated", ctypes.c_double),
+        ("range", ctypes.c_double),
+        ("momentary_max", ctypes.c_double),
+        ("short_term_max", ctypes.c_double),
+        ("true_peak", ctypes.c_double),
+        ("sample_peak", ctypes.c_double),
+        ("sub_blocks", ctypes.c_int64),
+        ("sub_block_frames", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
 PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
@@ -146,6 +162,9 @@ SYMBOLS = {
                                          c_int64_p]),
     "mgx_window_energy": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_double_p,
                                          ctypes.c_int64, c_int64_p]),
+    "mgx_loudness": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport), c_double_p,
+                                    ctypes.c_int64, c_int64_p]),
+    "mgx_loudness_gate": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport)]),
     "mgx_preview_cut": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_double, _VP]),
     "mgx_last_fir": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), c_int32_p]),

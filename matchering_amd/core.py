@@ -186,7 +186,10 @@ def _write_results(results, renderings, sample_rate):
 
 
 def process(target: str, reference: str, results: list, config: Config = None,
-            preview_target: Result = None, preview_result: Result = None):
+            preview_target: Result = None, preview_result: Result = None, loudness=None):
+    # (``loudness``: no counterpart in the reference -- a callable that receives (name, loudness.Loudness) for "target",
+    # for "reference" when its audio was loaded, and for each rendering the results need ("result", "result_no_limiter",
+    # "result_no_limiter_normalized"), measured on the frames in HBM; None: nothing is measured, nothing else changes)
     config = Config() if config is None else config
     debug("matchering_amd: the MI355X path behind the API of https://github.com/sergree/matchering")
     debug_line()
@@ -215,6 +218,8 @@ def process(target: str, reference: str, results: list, config: Config = None,
                                  (_file_encoding(preview_target), _file_encoding(preview_result)))
     encodings = None if (previews and request is None) else _wanted_encodings(results)
     extra = {"preview": request} if request is not None else {}
+    if loudness is not None:
+        extra["loudness"] = loudness
     renderings = main(resident[0] if resident[0] is not None else target_audio,
                       resident[1] if resident[1] is not None else reference_audio,
                       config, *_wanted_renderings(results), encodings=encodings, **extra)   # (releases the resident frames)

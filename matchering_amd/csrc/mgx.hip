@@ -24,6 +24,8 @@ static inline int roctxRangePop() { return 0; }
 #include "fir_design.h"
 #include "fir_plan.h"
 #include "host_params.h"
+#include "loudness_kernel.h"
+#include "loudness_plan.h"
 #include "mgx_kernels.h"
 #include "resample_kernel.h"
 #include "resample_plan.h"
@@ -144,6 +146,13 @@ struct mgx_handle {
     };
     std::map<std::pair<int, int>, ResampleDev> resample_plans;
     long long resample_designs = 0;         // plans designed and uploaded so far (mgx_resample_plan)
+    // mgx_loudness: the K-weighting plan of every sample rate this handle has metered, and its table on the device
+    struct LoudnessDev {
+        LoudnessPlan plan;
+        DevBuf table;
+    };
+    std::map<int, LoudnessDev> loudness_plans;
+    DevBuf loudness_out;                    // [nsub][2] sub-block energies, then [workgroups][2] peaks
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // set by a kernel whose bounded wait expired (limiter look-back, level-correction round): one word of
@@ -1164,7 +1173,8 @@ static int run_limiter(mgx_handle* h, const float* y, long long n, const Limiter
 // synchronisation, or a download of its outputs is already queued behind it (only the last call could be run again,
 // and a copy would have taken the failed run's frames) -- an expired tail fails like any other expired wait; the handle
 // still switches to one launch per round, so the caller's retry succeeds.
-static int check_device_error(mgx_handle* h, bool may_requeue = false) {
+// `whose`: what the caller handed in, for the report of a NaN or an infinity ("the frames to measure"); null: a pair.
+static int check_device_error(mgx_handle* h, bool may_requeue = false, const char* whose = nullptr) {
     h->requeued = false;
     const int outstanding = h->masters_outstanding;
     const int copies = h->downloads_outstanding;
@@ -1200,6 +1210,8 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
                                            : " differs from the Config's; a profile is used with the Config it was made with") +
                                       "; the outputs of the calls since the last synchronisation are not valid");
     }
+    if ((what & DEVICE_ERROR_INPUT) && whose)
+        return fail(MGX_ERR_ARGUMENT, std::string(whose) + " hold samples that are not finite numbers (NaN or infinity)");
     if (what & DEVICE_ERROR_INPUT)
         return fail(MGX_ERR_ARGUMENT, "the target or the reference holds samples that are not finite numbers (NaN or infinity): "
                                       "the reference fails on such input too (match_frequencies.py:42)");
@@ -1248,7 +1260,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false) {
 // ---------------------------------------------------------------------------
 extern "C" {
 
-int mgx_version(void) { return 103; }
+int mgx_version(void) { return 104; }
 const char* mgx_last_error(void) { return g_error.c_str(); }
 
 int mgx_device_count(int* count) {
@@ -1619,6 +1631,85 @@ int mgx_peak_count(mgx_handle* h, const float* x_dev, int64_t samples, double* p
     std::memcpy(&f, &bits, 4);
     *peak = (double)f;
     *count = (int64_t)host[1];
+    return 0;
+}
+
+static void loudness_fill(const LoudnessGated& g, int64_t nsub, int S, mgx_loudness_report* report) {
+    report->integrated = g.integrated;
+    report->range = g.range;
+    report->momentary_max = g.momentary_max;
+    report->short_term_max = g.short_term_max;
+    report->sub_blocks = nsub;
+    report->sub_block_frames = S;
+    report->reserved = 0;
+}
+
+int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_rate, mgx_loudness_report* report) {
+    if (!report || count < 0 || (count > 0 && !sub_energy)) return fail(MGX_ERR_ARGUMENT, "null argument or negative count");
+    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "loudness is metered at sample rates of 8000 Hz and above");
+    const int S = (sample_rate + 5) / 10;
+    loudness_fill(loudness_gate(sub_energy, count, S), count, S, report);
+    return 0;
+}
+
+int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_rate, mgx_loudness_report* report,
+                 double* sub_energy, int64_t capacity, int64_t* count) {
+    // everything that depends on the numbers alone is settled before the handle is touched
+    if (!report) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "loudness is metered at sample rates of 8000 Hz and above");
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
+    if (n > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_loudness: tracks of more than 500 million frames are not metered here");
+    const int S = (sample_rate + 5) / 10;
+    const int64_t nsub = n / S;
+    if (count) *count = nsub;
+    if (sub_energy && capacity < nsub) return fail(MGX_ERR_ARGUMENT, "the energy array holds fewer sub-blocks than the track has");
+    if (!h || (n > 0 && !x_dev)) return fail(MGX_ERR_ARGUMENT, "null argument");
+    report->true_peak = report->sample_peak = 0.0;
+    if (n == 0) {
+        loudness_fill(loudness_gate(nullptr, 0, S), 0, S, report);
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    mgx_handle::LoudnessDev& dev = h->loudness_plans[sample_rate];
+    if (!dev.table.p) {
+        dev.plan = loudness_design(sample_rate);
+        MGX_TRY(ensure(h, dev.table, dev.plan.table.size() * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(dev.table.p, dev.plan.table.data(), dev.plan.table.size() * sizeof(double), hipMemcpyHostToDevice,
+                               h->stream));
+    }
+    const LoudnessGeometry g = loudness_geometry(dev.plan, n);
+    const size_t doubles = (size_t)g.nsub * 2 + (size_t)g.workgroups * 2;
+    MGX_TRY(ensure(h, h->loudness_out, doubles * sizeof(double)));
+    MGX_TRY(ensure_pinned(h, std::max(doubles * sizeof(double), (size_t)1 << 16)));
+    LoudnessArgs a;
+    a.x = x_dev;
+    a.n = n;
+    a.table = (const double*)dev.table.p;
+    std::memcpy(a.c, dev.plan.c, sizeof a.c);
+    a.S = g.S;
+    a.own = g.own;
+    a.warmup = g.warmup;
+    a.nsub = g.nsub;
+    a.e = (double*)h->loudness_out.p;
+    a.peaks = a.e + (size_t)g.nsub * 2;
+    a.error = h->error_dev;
+    a.error_slot = DEVICE_ERROR_SLOT_INPUT;
+    MGX_TRY(allow_lds(k_loudness, LOUD_LDS_BYTES));
+    hipLaunchKernelGGL(k_loudness, dim3((unsigned)g.workgroups), dim3(LOUD_THREADS), LOUD_LDS_BYTES, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->pinned, h->loudness_out.p, doubles * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // (as every blocking call: this also takes whatever the calls queued before it have reported, and with it the
+    // handle's count of mgx_master calls and downloads outstanding -- nothing of theirs can be queued again from here)
+    MGX_TRY(check_device_error(h, false, "the frames to measure"));
+    const double* e = (const double*)h->pinned;
+    const double* peaks = e + (size_t)g.nsub * 2;
+    for (int64_t w = 0; w < g.workgroups; ++w) {
+        report->true_peak = std::max(report->true_peak, peaks[2 * w]);
+        report->sample_peak = std::max(report->sample_peak, peaks[2 * w + 1]);
+    }
+    loudness_fill(loudness_gate(e, g.nsub, g.S), g.nsub, g.S, report);
+    if (sub_energy) std::memcpy(sub_energy, e, (size_t)g.nsub * 2 * sizeof(double));
     return 0;
 }
 

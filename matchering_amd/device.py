@@ -393,6 +393,22 @@ class Device:
                                        ctypes.byref(count)))
         return peak.value, count.value
 
+    def loudness(self, buf, frames, rate, sub_energy=False):
+        """BS.1770-4 loudness and true peak of (frames, 2) float32 in HBM at ``rate`` Hz (``mgx_loudness``): a
+        ``loudness.Loudness``; with ``sub_energy=True`` also the (frames // S, 2) K-weighted sub-block energies."""
+        from .loudness import from_report
+
+        report, got = _native.MgxLoudnessReport(), ctypes.c_int64()
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        capacity = int(frames) // ((int(rate) + 5) // 10) if sub_energy and rate > 0 else 0
+        energy = np.zeros((capacity, 2)) if sub_energy else None
+        check(library().mgx_loudness(self.handle, ctypes.c_void_p(ptr), int(frames), int(rate), ctypes.byref(report),
+                                     None if energy is None else energy.ctypes.data_as(_native.c_double_p), capacity,
+                                     ctypes.byref(got)))
+        self._keep_until_sync.clear()          # (the call has waited for the stream: the uploads queued before it are done)
+        value = from_report(report, rate, frames)
+        return (value, energy) if sub_energy else value
+
     def download_pcm(self, buf, frames, channels, bits, wait=True):
         """float32 frames in HBM -> integer PCM on the host (pinned): int16 / int32 (n, channels), or uint8
         (n, channels * 3) for packed 24-bit.  Quantised on the device as libsndfile would on the host."""

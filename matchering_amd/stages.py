@@ -46,7 +46,7 @@ def _is_profile(reference):
 
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
-         encodings=None, preview=None):
+         encodings=None, preview=None, loudness=None):
     # (``device``: the handle to run on, default the process-wide one; ``fir``: a DeviceBuffer with a
     # matching FIR to apply instead of designing one -- batch.master_album; ``encodings``: per output,
     # None for float32 frames or "PCM_16" / "PCM_24" / "PCM_32" for the integer samples a file of that
@@ -56,7 +56,10 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # preview.PreviewRequest -- the A/B previews of preview_creator.py:30-94 are cut from the first requested
     # output and from the target while both are still in HBM, and left in the request.  ``reference`` may be a
     # profile.ReferenceProfile: the reference's analysis results without its audio, made with this Config --
-    # mgx_master_with_profile; stage 1 then runs on the target alone.)
+    # mgx_master_with_profile; stage 1 then runs on the target alone.  ``loudness``: a callable that receives
+    # (name, loudness.Loudness) for "target", for "reference" when its audio is here, and for each requested output --
+    # "result", "result_no_limiter", "result_no_limiter_normalized" -- measured on the float frames in HBM
+    # (mgx_loudness), before any encoding; None: nothing is measured.)
     dev = device if device is not None else default_device()
     target = _as_frames(target, "target")
     profile = reference if _is_profile(reference) else None
@@ -106,6 +109,14 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                 debug(f"unlimited result normalised by {to_db(report.normalize_coefficient)} to reach the threshold")
             if need_default and not report.limiter_active:
                 debug("the result stays under the threshold: the limiter passes it through")
+            if loudness is not None:
+                rate = config.internal_sample_rate
+                loudness("target", dev.loudness(t_dev, n, rate))
+                if r_dev is not None:
+                    loudness("reference", dev.loudness(r_dev, nr, rate))
+                for name, b in zip(("result", "result_no_limiter", "result_no_limiter_normalized"), outs):
+                    if b is not None:
+                        loudness(name, dev.loudness(b, n, rate))
             # queued one behind the other, then ONE wait; the arrays live in pinned host memory
             formats = encodings if encodings is not None else (None, None, None)
             pieces = []
