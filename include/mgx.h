@@ -329,6 +329,56 @@ int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_ra
                  double* sub_energy, int64_t capacity, int64_t* count);
 int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_rate, mgx_loudness_report* report);
 
+/* Delivery renditions: a rendering written AT a delivery specification -- a loudness target, a true-peak ceiling,
+ * dithered integer PCM -- from frames that are still in HBM (the reference has none of this; saver.py:27-33 rounds
+ * without dither).  Part of the new surface, like the meter it builds on.
+ * mgx_delivery_gain is the policy, on the host, from a measurement of mgx_loudness; needs no GPU.  Linear gain only --
+ * what EBU R 128 normalisation is -- never an approximation of a limiter:
+ *     g_loud = 10^((target_lufs - integrated) / 20)      1 without a target, or where integrated is -infinity
+ *     g_peak = (10^(ceiling_dbtp / 20) - A e / 2^(bits-1)) / true_peak      +infinity without a ceiling or at true_peak 0
+ *     gain   = min(g_loud, g_peak)
+ * A e / 2^(bits-1) is the quantiser's head-room: A = the largest per-phase sum of the meter's absolute oversampling taps
+ * (phase 2: 1.76294455...), computed from the taps themselves; e = the most that dither and rounding add to a sample in
+ * LSB: 0.5 without dither, 1.5 with either, 0 for float output.  With it the ceiling holds for the written file as the
+ * meter reads it back (decoded by v / 2^(bits-1)): DESIGN.md section 3.11 has the derivation.
+ * limited_by: 2 where the ceiling set the gain (g_peak < g_loud), else 1 where a loudness target did, else 0 (nothing was
+ * asked for, or nothing that was asked for changes the gain).  shortfall_lu = target_lufs - achieved_lufs where the ceiling
+ * kept the loudness below the target, else 0.
+ * MGX_ERR_ARGUMENT, the message naming the field: a null argument; ceiling_dbtp above 0 (clipping would break the bound) or
+ * so low that the head-room leaves g_peak nothing; an infinite target_lufs or ceiling_dbtp; bits outside {0, 16, 24, 32};
+ * dither outside {0, 1, 2}, or dither with bits 0 or 32; a measured true_peak that is negative or not finite, a measured
+ * integrated that is NaN or +infinity. */
+typedef struct mgx_delivery {
+    double target_lufs;                  /* NaN: no loudness target */
+    double ceiling_dbtp;                 /* NaN: no ceiling; otherwise <= 0 */
+    int32_t bits;                        /* 0 = float32 out, or 16, 24, 32 */
+    int32_t dither;                      /* 0 none, 1 TPDF, 2 high-passed TPDF */
+    uint64_t seed;
+} mgx_delivery;
+typedef struct mgx_delivery_result {
+    double gain;                         /* linear */
+    double achieved_lufs;                /* integrated + 20 log10(gain); -infinity where integrated is */
+    double achieved_true_peak;           /* gain * true_peak, linear: as predicted from the measurement */
+    double shortfall_lu;                 /* >= 0 */
+    int32_t limited_by;                  /* 0 nothing, 1 loudness, 2 true peak */
+    int32_t reserved;
+} mgx_delivery_result;
+int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* measured, mgx_delivery_result* result);
+/* One pass over interleaved float32 samples in HBM: gain, dither, quantise, pack.  `samples` counts single samples, as
+ * mgx_pcm_encode does; out_dev receives `samples` float32 (bits 0), int16, packed 24-bit or int32 values.  With
+ * top = 2^(bits-1) - 1:
+ *     a = ((double)x[s] * gain) * top;     v = clip(rint(a + d(s)), -top - 1, top)        bits 0: out[s] = (float)(x[s] * gain)
+ * d = 0 without dither: at gain 1.0 the output is mgx_pcm_encode's, byte for byte.  The random numbers are Philox4x32-10
+ * (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85), key = (seed low word, seed high word),
+ * counter = (q low, q high, stream, 0) with q = s >> 2; W(s, stream) = output word s & 3;
+ * U(s, stream) = ((W >> 8) + 0.5) 2^-24 - 0.5, 0 for s < 0.  TPDF: d(s) = U(s, 0) + U(s, 1).  High-passed TPDF:
+ * d(s) = U(s, 0) - U(s - 2, 0), the same channel one frame earlier: triangular density, first-differenced spectrum, no
+ * error feedback.  Every value is defined bit for bit (tests/delivery_oracle.py).  Queued on the handle's stream; waits
+ * for nothing.  x_dev and out_dev must be 16-byte aligned (what mgx_malloc returns is).  MGX_ERR_ARGUMENT: a null
+ * argument, negative samples, a misaligned pointer, a gain that is not finite, bits or dither as for mgx_delivery_gain. */
+int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain, int32_t bits, int32_t dither,
+                uint64_t seed, void* out_dev);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

@@ -103,6 +103,31 @@ class MgxLoudnessReport(ctypes.Structure):
     ]
 
 
+class MgxDelivery(ctypes.Structure):
+    """mgx_delivery (include/mgx.h)."""
+
+    _fields_ = [
+        ("target_lufs", ctypes.c_double),
+        ("ceiling_dbtp", ctypes.c_double),
+        ("bits", ctypes.c_int32),
+        ("dither", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+    ]
+
+
+class MgxDeliveryResult(ctypes.Structure):
+    """mgx_delivery_result (include/mgx.h)."""
+
+    _fields_ = [
+        ("gain", ctypes.c_double),
+        ("achieved_lufs", ctypes.c_double),
+        ("achieved_true_peak", ctypes.c_double),
+        ("shortfall_lu", ctypes.c_double),
+        ("limited_by", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
 PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
@@ -165,6 +190,10 @@ SYMBOLS = {
     "mgx_loudness": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport), c_double_p,
                                     ctypes.c_int64, c_int64_p]),
     "mgx_loudness_gate": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport)]),
+    "mgx_delivery_gain": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxLoudnessReport),
+                                         ctypes.POINTER(MgxDeliveryResult)]),
+    "mgx_deliver": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                   _VP]),
     "mgx_preview_cut": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_double, _VP]),
     "mgx_last_fir": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), c_int32_p]),

@@ -27,7 +27,8 @@ and on a node with 8 GPUs::
         -m matchering_amd.batch jobs.json
 
 ``jobs.json`` is a list of ``{"target": path, "reference": path, "results": [{"file": path,
-"subtype": "PCM_16", "use_limiter": true, "normalize": true}, ...]}``; in place of ``"reference"`` a job may name a
+"subtype": "PCM_16", "use_limiter": true, "normalize": true, "delivery": {"loudness": -14, "true_peak": -1,
+"dither": "tpdf_hp", "seed": 0}}, ...]}`` (``"delivery"`` and each of its keys optional: ``delivery.Delivery``); in place of ``"reference"`` a job may name a
 ``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
 list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).
 """
@@ -254,15 +255,20 @@ def lane_device(device_index, lane):
 
 def _device_worker(device_index, lane, config, needs, master, encodings=None):
     """A callable mastering one (target, reference) array pair on the lane's own device handle.
-    ``encodings``: stages.main's (integer PCM renderings straight from the GPU)."""
+    ``encodings``: stages.main's (integer PCM renderings straight from the GPU).  ``deliveries`` (per call): a job's
+    ``delivery.DeliveryRequest``, handed to ``main`` where the job has one."""
+    def extra(deliveries):
+        return {"deliveries": deliveries} if deliveries else {}
+
     if master is not None:                         # tests inject a stand-in for the GPU
         if encodings is None or not any(encodings):
-            return lambda pair: master(pair[0], pair[1], config, *needs)
-        return lambda pair: master(pair[0], pair[1], config, *needs, encodings=encodings)
+            return lambda pair, deliveries=None: master(pair[0], pair[1], config, *needs, **extra(deliveries))
+        return lambda pair, deliveries=None: master(pair[0], pair[1], config, *needs, encodings=encodings, **extra(deliveries))
     from .stages import main
 
     dev = lane_device(device_index, lane)
-    return lambda pair: main(pair[0], pair[1], config, *needs, device=dev, encodings=encodings)
+    return lambda pair, deliveries=None: main(pair[0], pair[1], config, *needs, device=dev, encodings=encodings,
+                                              **extra(deliveries))
 
 
 def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
@@ -538,13 +544,25 @@ def _load_job(job, config, gpu=False, shared=False):
     return target, reference, later
 
 
-def _save_job(job, triple, config):
+class _WithDeliveries(tuple):
+    """A job's triple of renderings with the ``DeliveryRequest`` that ``stages.main`` filled beside it."""
+
+    def __new__(cls, triple, deliveries):
+        self = super().__new__(cls, triple)
+        self.deliveries = deliveries
+        return self
+
+
+def _save_job(job, triple, config, deliveries=None):
     from .audio_io import save
+    from .delivery import plain_results, write_deliveries
 
     result, plain, normalized = triple
-    for wanted in job["results"]:
+    for wanted in plain_results(job["results"]):
         chosen = result if wanted.use_limiter else (normalized if wanted.normalize else plain)
         save(wanted.file, chosen, config.internal_sample_rate, wanted.subtype)
+    if deliveries:
+        write_deliveries(job["results"], deliveries, config.internal_sample_rate)
 
 
 def process_batch(jobs, config=None, rank=None, world_size=None, device_index=None, lanes=None, io_threads=4,
@@ -620,13 +638,21 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                         if reference.key not in merged:
                             merged[reference.key] = merged_set(reference)
                         reference = merged[reference.key]
-                needs = _needs_of(jobs[index]["results"])
-                key = (needs, _wanted_encodings(jobs[index]["results"]))
+                from .delivery import DeliveryRequest, plain_results
+
+                # (results with a delivery come back in the job's DeliveryRequest: they decide neither which renderings
+                # are returned nor their encodings)
+                ordinary = plain_results(jobs[index]["results"])
+                deliveries = DeliveryRequest.for_results(jobs[index]["results"])
+                needs = _needs_of(ordinary)
+                key = (needs, _wanted_encodings(ordinary))
                 if key not in workers:
                     workers[key] = _device_worker(device_index, lane, config, needs, master, key[1])
                 if later is not None:
                     target, reference = _on_the_lane(target, reference, later, device_index, lane, config, master)
-                return workers[key]((target, reference))
+                if not deliveries:
+                    return workers[key]((target, reference))
+                return _WithDeliveries(workers[key]((target, reference), deliveries), deliveries)
             return run
 
         if lanes is None:
@@ -641,7 +667,7 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
         def done(index, triple, exc):
             if exc is None:
                 unsaved.acquire()
-                future = io.submit(_save_job, jobs[index], triple, config)
+                future = io.submit(_save_job, jobs[index], tuple(triple), config, getattr(triple, "deliveries", None))
                 future.add_done_callback(lambda _f: unsaved.release())
                 savers.append(future)
 
@@ -674,8 +700,12 @@ def jobs_from_json(path):
         raw = json.load(fh)
     jobs = []
     for item in raw:
+        from .delivery import Delivery
+
         results = [Result(r["file"], subtype=r.get("subtype", "PCM_16"), use_limiter=r.get("use_limiter", True),
-                          normalize=r.get("normalize", True)) for r in item["results"]]
+                          normalize=r.get("normalize", True),
+                          delivery=None if r.get("delivery") is None else Delivery.from_json(r["delivery"]))
+                   for r in item["results"]]
         job = {"target": item["target"], "results": results}
         for key in REFERENCE_KEYS:
             if item.get(key) is not None:

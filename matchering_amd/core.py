@@ -18,6 +18,7 @@ import numpy as np
 from .audio_io import load, pcm_channels, pcm_to_float, save
 from .checker import check, check_equality
 from .config import Config
+from .delivery import DeliveryRequest, plain_results, write_deliveries
 from .log import Code, ModuleError, debug, debug_line, info
 from .preview import PreviewRequest, create_preview, save_previews
 from .results import Result
@@ -177,12 +178,15 @@ def _same_file(a, b):
         return False
 
 
-def _write_results(results, renderings, sample_rate):
-    """One file per Result, each from the rendering it asked for (core.py:95-108)."""
+def _write_results(results, renderings, sample_rate, deliveries=None):
+    """One file per Result, each from the rendering it asked for (core.py:95-108); a Result with a delivery from the
+    array ``stages.main`` left in the ``DeliveryRequest``."""
     limited, plain, normalized = renderings
-    for item in results:
+    for item in plain_results(results):
         audio = limited if item.use_limiter else (normalized if item.normalize else plain)
         save(item.file, audio, sample_rate, item.subtype)
+    if deliveries:
+        write_deliveries(results, deliveries, sample_rate)
 
 
 def process(target: str, reference: str, results: list, config: Config = None,
@@ -216,13 +220,19 @@ def process(target: str, reference: str, results: list, config: Config = None,
     if previews and _gpu() is not None:
         request = PreviewRequest(config, preview_target, preview_result,
                                  (_file_encoding(preview_target), _file_encoding(preview_result)))
-    encodings = None if (previews and request is None) else _wanted_encodings(results)
+    # results with a delivery are cut from the renderings in HBM and come back in the DeliveryRequest: they take no part
+    # in which renderings are returned, or in the "one subtype per rendering" rule of _wanted_encodings
+    ordinary = plain_results(results)
+    deliveries = DeliveryRequest.for_results(results)
+    encodings = None if (previews and request is None) else _wanted_encodings(ordinary)
     extra = {"preview": request} if request is not None else {}
     if loudness is not None:
         extra["loudness"] = loudness
+    if deliveries:
+        extra["deliveries"] = deliveries
     renderings = main(resident[0] if resident[0] is not None else target_audio,
                       resident[1] if resident[1] is not None else reference_audio,
-                      config, *_wanted_renderings(results), encodings=encodings, **extra)   # (releases the resident frames)
+                      config, *_wanted_renderings(ordinary), encodings=encodings, **extra)   # (releases the resident frames)
     del reference_audio
 
     debug_line()
@@ -231,12 +241,14 @@ def process(target: str, reference: str, results: list, config: Config = None,
         # the target may be a read-only mapping of its file (audio_io.read_wav): a result written over that
         # file would pull the mapping from under the preview cut below
         target_audio = np.array(target_audio, copy=True)
-    _write_results(results, renderings, config.internal_sample_rate)
+    _write_results(results, renderings, config.internal_sample_rate, deliveries)
 
     if request is not None:
         save_previews(request, config, preview_target, preview_result)
     elif previews:
-        mastered = next(audio for audio in renderings if audio is not None)
+        mastered = next((audio for audio in renderings if audio is not None), None)
+        if mastered is None:                                   # every result is a delivery: the first of them
+            mastered = pcm_to_float(deliveries.arrays[results[0].file])
         create_preview(pcm_to_float(target_audio), mastered, config, preview_target, preview_result)
 
     debug_line()

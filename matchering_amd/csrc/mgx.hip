@@ -29,6 +29,7 @@ static inline int roctxRangePop() { return 0; }
 #include "mgx_kernels.h"
 #include "resample_kernel.h"
 #include "resample_plan.h"
+#include "deliver_kernel.h"            // (behind every other kernel: it moves none of them in the code object)
 
 using namespace mgx;
 
@@ -1260,7 +1261,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false, const cha
 // ---------------------------------------------------------------------------
 extern "C" {
 
-int mgx_version(void) { return 104; }
+int mgx_version(void) { return 105; }
 const char* mgx_last_error(void) { return g_error.c_str(); }
 
 int mgx_device_count(int* count) {
@@ -1774,6 +1775,80 @@ int mgx_pcm_encode(mgx_handle* h, const float* x_dev, int64_t samples, int32_t b
     HIP_TRY(hipSetDevice(h->device));
     const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 8192);
     hipLaunchKernelGGL(k_pcm_encode, dim3(grid), dim3(256), 0, h->stream, x_dev, (long long)samples, bits, pcm_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the arguments mgx_delivery_gain and mgx_deliver share
+static int deliver_format_check(int32_t bits, int32_t dither) {
+    if (bits != 0 && bits != 16 && bits != 24 && bits != 32)
+        return fail(MGX_ERR_ARGUMENT, "bits: a delivery is float32 (0) or 16, 24 or 32-bit PCM");
+    if (dither < 0 || dither > 2) return fail(MGX_ERR_ARGUMENT, "dither: 0 (none), 1 (TPDF) or 2 (high-passed TPDF)");
+    if (dither != 0 && (bits == 0 || bits == 32))
+        return fail(MGX_ERR_ARGUMENT, "dither: only 16 and 24-bit deliveries are dithered");
+    return 0;
+}
+
+int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* measured, mgx_delivery_result* result) {
+    if (!delivery || !measured || !result) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(deliver_format_check(delivery->bits, delivery->dither));
+    const double target = delivery->target_lufs, ceiling = delivery->ceiling_dbtp;
+    const double integrated = measured->integrated, peak = measured->true_peak;
+    if (std::isinf(target)) return fail(MGX_ERR_ARGUMENT, "target_lufs: must be finite (NaN: no target)");
+    if (std::isinf(ceiling)) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: must be finite (NaN: no ceiling)");
+    if (ceiling > 0.0) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: a ceiling above 0 dBTP would clip");
+    if (!std::isfinite(peak) || peak < 0.0) return fail(MGX_ERR_ARGUMENT, "true_peak: the measured peak is negative or not finite");
+    if (std::isnan(integrated) || integrated == INFINITY)
+        return fail(MGX_ERR_ARGUMENT, "integrated: the measured loudness is NaN or +infinity");
+    const bool has_loud = !std::isnan(target) && std::isfinite(integrated);
+    const double g_loud = has_loud ? std::pow(10.0, (target - integrated) / 20.0) : 1.0;
+    double g_peak = INFINITY;
+    if (!std::isnan(ceiling)) {
+        // A: the most the meter's interpolator makes of errors of magnitude 1 -- the largest per-phase sum of |taps|
+        double taps[49], A = 0.0;
+        loudness_true_peak_taps(taps);
+        for (int p = 0; p < 4; ++p) {
+            double sum = 0.0;
+            for (int k = p; k < 49; k += 4) sum += std::fabs(taps[k]);
+            A = std::max(A, sum);
+        }
+        const double e = delivery->bits == 0 ? 0.0 : (delivery->dither ? 1.5 : 0.5);
+        const double margin = delivery->bits == 0 ? 0.0 : A * e / std::ldexp(1.0, delivery->bits - 1);
+        const double room = std::pow(10.0, ceiling / 20.0) - margin;
+        if (!(room > 0.0))
+            return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: lower than the quantiser's own head-room at this width");
+        if (peak > 0.0) g_peak = room / peak;
+    }
+    const double gain = std::min(g_loud, g_peak);
+    result->gain = gain;
+    result->achieved_lufs = std::isfinite(integrated) ? integrated + 20.0 * std::log10(gain) : -INFINITY;
+    result->achieved_true_peak = gain * peak;
+    const bool by_peak = g_peak < g_loud;
+    result->shortfall_lu = by_peak && has_loud ? 20.0 * std::log10(g_loud / gain) : 0.0;
+    result->limited_by = by_peak ? 2 : (has_loud ? 1 : 0);
+    result->reserved = 0;
+    return 0;
+}
+
+int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain, int32_t bits, int32_t dither,
+                uint64_t seed, void* out_dev) {
+    if (!h || !x_dev || !out_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(deliver_format_check(bits, dither));
+    if (samples < 0) return fail(MGX_ERR_ARGUMENT, "samples: negative");
+    if (!std::isfinite(gain)) return fail(MGX_ERR_ARGUMENT, "gain: not a finite number");
+    if ((((size_t)x_dev) | ((size_t)out_dev)) & 15) return fail(MGX_ERR_ARGUMENT, "x_dev / out_dev: must be 16-byte aligned");
+    if (samples == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    DeliverArgs a;
+    a.x = x_dev;
+    a.samples = samples;
+    a.gain = gain;
+    a.bits = bits;
+    a.dither = dither;
+    a.key0 = (unsigned)seed;
+    a.key1 = (unsigned)(seed >> 32);
+    a.out = out_dev;
+    hipLaunchKernelGGL(k_deliver, dim3((unsigned)deliver_grid(samples)), dim3(DELIVER_THREADS), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,187 @@
+"""Delivery renditions: a result written AT a delivery specification -- a loudness target, a true-peak ceiling, dithered
+integer PCM -- from the frames ``stages.main`` still holds in HBM.  The reference has none of this (saver.py:27-33 rounds
+without dither, and its limiter's ceiling, hyrax.py:78-99, is a sample-peak ceiling).
+
+    import matchering_amd as mg
+    mg.process(target, reference, [
+        mg.pcm24("streaming.wav", delivery=mg.Delivery(loudness=-14.0, true_peak=-1.0)),
+        mg.pcm16("cd.wav", delivery=mg.Delivery(dither="tpdf_hp")),
+        mg.pcm24("master.wav"),
+    ])
+
+The rendering is measured once (``mgx_loudness``), ``mgx_delivery_gain`` turns the measurement into ONE linear gain -- what
+EBU R 128 normalisation is; never an approximation of a limiter -- and ``mgx_deliver`` applies it, dithers, quantises and
+packs in one pass.  The ceiling holds for the written file as a BS.1770 meter reads it back: the gain leaves the quantiser
+its head-room (include/mgx.h).  Where the ceiling keeps the loudness under the target the
+``Delivered`` record says by how much (``shortfall_lu``).
+"""
+
+import ctypes
+import math
+from dataclasses import dataclass
+
+from .loudness import Loudness, _db
+
+DITHERS = {None: 0, "tpdf": 1, "tpdf_hp": 2}
+SUBTYPE_BITS = {"PCM_16": 16, "PCM_24": 24, "PCM_32": 32}            # every other subtype is delivered as float32 frames
+LIMITED_BY = (None, "loudness", "true_peak")
+
+
+@dataclass(frozen=True)
+class Delivery:
+    """What a result is to meet.  ``loudness``: integrated loudness in LUFS, ``true_peak``: the ceiling in dBTP (at most
+    0), either may be None; ``dither``: None, "tpdf" or "tpdf_hp" (high-passed TPDF), for 16 and 24-bit files;
+    ``seed``: the dither generator's key -- the same seed writes the same file."""
+
+    loudness: float = None
+    true_peak: float = None
+    dither: str = None
+    seed: int = 0
+
+    def __post_init__(self):
+        for name in ("loudness", "true_peak"):
+            value = getattr(self, name)
+            if value is not None and not (isinstance(value, (int, float)) and math.isfinite(value)):
+                raise ValueError(f"Delivery: {name} must be a finite number or None, got {value!r}")
+        if self.true_peak is not None and self.true_peak > 0.0:
+            raise ValueError(f"Delivery: a true-peak ceiling above 0 dBTP would clip, got {self.true_peak!r}")
+        if self.dither not in DITHERS:
+            raise ValueError(f"Delivery: dither must be None, 'tpdf' or 'tpdf_hp', got {self.dither!r}")
+        if not (isinstance(self.seed, int) and 0 <= self.seed < 2 ** 64):
+            raise ValueError(f"Delivery: seed must be an integer in [0, 2**64), got {self.seed!r}")
+
+    def check_subtype(self, subtype):
+        """The error ``Result`` raises at construction for a width this delivery cannot be written at."""
+        if self.dither is not None and subtype not in ("PCM_16", "PCM_24"):
+            raise ValueError(f"Delivery: dither is for PCM_16 and PCM_24 results, not {subtype}")
+
+    def native(self, bits):
+        from ._native import MgxDelivery
+
+        return MgxDelivery(math.nan if self.loudness is None else float(self.loudness),
+                           math.nan if self.true_peak is None else float(self.true_peak), int(bits),
+                           DITHERS[self.dither], int(self.seed))
+
+    @classmethod
+    def from_json(cls, entry):
+        """``{"loudness": ..., "true_peak": ..., "dither": ..., "seed": ...}`` of a batch job (every key optional)."""
+        if isinstance(entry, cls):
+            return entry
+        if not isinstance(entry, dict):
+            raise ValueError(f"a delivery is an object with loudness / true_peak / dither / seed, got {entry!r}")
+        unknown = set(entry) - {"loudness", "true_peak", "dither", "seed"}
+        if unknown:
+            raise ValueError(f"delivery: unknown keys {sorted(unknown)}")
+        return cls(**entry)
+
+
+@dataclass(frozen=True)
+class Delivered:
+    """What became of one delivery: ``mgx_delivery_result``'s fields, the measurement they were derived from and the
+    request.  ``achieved_lufs`` / ``achieved_true_peak`` (linear) are predicted from the measurement of the rendering."""
+
+    gain: float
+    achieved_lufs: float
+    achieved_true_peak: float
+    shortfall_lu: float
+    limited_by: str                 # None, "loudness" or "true_peak"
+    measured: Loudness
+    delivery: Delivery
+    bits: int
+
+    @property
+    def gain_db(self):
+        return _db(self.gain)
+
+    @property
+    def achieved_true_peak_db(self):
+        """dBTP"""
+        return _db(self.achieved_true_peak)
+
+    def __str__(self):
+        text = (f"gain {self.gain_db:+.2f} dB: {self.achieved_lufs:.2f} LUFS, true peak {self.achieved_true_peak_db:.2f} dBTP "
+                f"({'float32' if self.bits == 0 else f'{self.bits} bit'}"
+                f"{'' if self.delivery.dither is None else ', ' + self.delivery.dither})")
+        if self.shortfall_lu > 0.0:
+            text += f"; the ceiling keeps it {self.shortfall_lu:.2f} LU under the {self.delivery.loudness:g} LUFS target"
+        return text
+
+
+def delivery_gain(delivery: Delivery, bits: int, measured: Loudness) -> Delivered:
+    """``mgx_delivery_gain`` (host only, needs no GPU): the gain that brings a rendering measured as ``measured`` to
+    ``delivery`` at ``bits`` (0: float32)."""
+    from . import _native
+
+    report = _native.MgxLoudnessReport()
+    report.integrated, report.true_peak = measured.integrated, measured.true_peak
+    out = _native.MgxDeliveryResult()
+    _native.check(_native.library().mgx_delivery_gain(ctypes.byref(delivery.native(bits)), ctypes.byref(report),
+                                                      ctypes.byref(out)))
+    return Delivered(out.gain, out.achieved_lufs, out.achieved_true_peak, out.shortfall_lu, LIMITED_BY[out.limited_by],
+                     measured, delivery, int(bits))
+
+
+RENDERINGS = ("result", "result_no_limiter", "result_no_limiter_normalized")
+
+
+class DeliveryRequest:
+    """What ``stages.main(..., deliveries=request)`` needs to cut the deliveries on the device, and where it leaves them
+    (the pattern of ``preview.PreviewRequest``).  ``items``: (key, rendering, subtype, Delivery) each -- ``rendering`` 0
+    the limited result, 1 the unlimited one, 2 the unlimited one normalised, as in ``main``'s triple; ``subtype`` a file
+    subtype: PCM_16 / PCM_24 / PCM_32 come back as the integer samples of such a file, everything else as float32
+    frames.  After ``main``: ``arrays[key]`` the host array, ``delivered[key]`` the ``Delivered`` record."""
+
+    def __init__(self, items=()):
+        self.items = []
+        self.arrays, self.delivered = {}, {}
+        for key, rendering, subtype, delivery in items:
+            self.add(key, rendering, subtype, delivery)
+
+    def add(self, key, rendering, subtype, delivery):
+        if rendering not in (0, 1, 2):
+            raise ValueError(f"DeliveryRequest: rendering must be 0, 1 or 2, got {rendering!r}")
+        if not isinstance(delivery, Delivery):
+            raise TypeError(f"DeliveryRequest: expected a Delivery, got {delivery!r}")
+        delivery.check_subtype(subtype)
+        if any(key == k for k, *_ in self.items):
+            raise ValueError(f"DeliveryRequest: {key!r} is delivered twice")
+        self.items.append((key, int(rendering), subtype, delivery))
+
+    @classmethod
+    def for_results(cls, results):
+        """The request of ``process``: one item per Result that carries a delivery, keyed by its file."""
+        request = cls()
+        for item in results:
+            if getattr(item, "delivery", None) is not None:
+                request.add(item.file, rendering_of(item), item.subtype, item.delivery)
+        return request
+
+    def needs(self):
+        """Which of ``main``'s three renderings the items are cut from."""
+        return tuple(any(r == slot for _, r, _, _ in self.items) for slot in range(3))
+
+    def __bool__(self):
+        return bool(self.items)
+
+
+def rendering_of(item):
+    """The rendering a ``Result`` is made from (core.py:99-108)."""
+    return 0 if item.use_limiter else (2 if item.normalize else 1)
+
+
+def plain_results(results):
+    """The results that take the ordinary route: no delivery."""
+    return [item for item in results if getattr(item, "delivery", None) is None]
+
+
+def write_deliveries(results, request, sample_rate):
+    """One file per Result that carries a delivery, from the arrays ``stages.main`` left in ``request``; one log line
+    each: gain, achieved LUFS and dBTP, and the shortfall where the ceiling bound the loudness."""
+    from .audio_io import save
+    from .log import debug
+
+    for item in results:
+        if getattr(item, "delivery", None) is None:
+            continue
+        debug(f"delivery '{item.file}': {request.delivered[item.file]}")
+        save(item.file, request.arrays[item.file], sample_rate, item.subtype)

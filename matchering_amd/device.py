@@ -424,6 +424,27 @@ class Device:
             self.synchronize()
         return out
 
+    def deliver(self, buf, frames, channels, gain, bits, dither=0, seed=0, wait=True):
+        """float32 frames in HBM -> a delivery rendition on the host (pinned), in one pass on the device
+        (``mgx_deliver``): every sample times ``gain``, dithered (0 none, 1 TPDF, 2 high-passed TPDF, keyed by ``seed``),
+        quantised and packed -- int16 / int32 (n, channels), uint8 (n, channels * 3) for packed 24-bit, or float32
+        (n, channels) for ``bits`` 0."""
+        samples = int(frames) * int(channels)
+        nbytes = samples * (bits // 8 if bits else 4)
+        out_dev = DeviceBuffer(self, max(nbytes, 1))
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        try:
+            check(library().mgx_deliver(self.handle, ctypes.c_void_p(ptr), samples, float(gain), int(bits), int(dither),
+                                        int(seed), ctypes.c_void_p(out_dev.ptr)))
+            shape, dtype = {0: ((frames, channels), np.float32), 16: ((frames, channels), np.int16),
+                            32: ((frames, channels), np.int32), 24: ((frames, channels * 3), np.uint8)}[int(bits)]
+            out = self.download(out_dev, shape, dtype, wait=False)
+        finally:
+            out_dev.release()   # (recycled by later work on this stream only, which is ordered behind the copy)
+        if wait:
+            self.synchronize()
+        return out
+
     # ---- previews on frames that are still in HBM (mgx_window_energy / mgx_preview_cut) ----------
     def window_energy(self, buf, frames, size, step):
         """dsp.py:128-143: sum of squares (both channels) of every window of ``size`` frames every ``step``."""

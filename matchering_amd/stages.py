@@ -46,7 +46,7 @@ def _is_profile(reference):
 
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
-         encodings=None, preview=None, loudness=None):
+         encodings=None, preview=None, loudness=None, deliveries=None):
     # (``device``: the handle to run on, default the process-wide one; ``fir``: a DeviceBuffer with a
     # matching FIR to apply instead of designing one -- batch.master_album; ``encodings``: per output,
     # None for float32 frames or "PCM_16" / "PCM_24" / "PCM_32" for the integer samples a file of that
@@ -59,7 +59,10 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # mgx_master_with_profile; stage 1 then runs on the target alone.  ``loudness``: a callable that receives
     # (name, loudness.Loudness) for "target", for "reference" when its audio is here, and for each requested output --
     # "result", "result_no_limiter", "result_no_limiter_normalized" -- measured on the float frames in HBM
-    # (mgx_loudness), before any encoding; None: nothing is measured.)
+    # (mgx_loudness), before any encoding; None: nothing is measured.  ``deliveries``: a delivery.DeliveryRequest --
+    # renditions of the renderings at a loudness target, under a true-peak ceiling, dithered (mgx_delivery_gain,
+    # mgx_deliver), made while the renderings are still in HBM and left in the request; a rendering that only a delivery
+    # names is computed but not returned, and ``loudness`` also receives ("delivered:" + key, delivery.Delivered).)
     dev = device if device is not None else default_device()
     target = _as_frames(target, "target")
     profile = reference if _is_profile(reference) else None
@@ -82,8 +85,9 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
             r_dev, p_dev = None, profile.resident(dev)       # (the profile's own buffer: kept, not released here)
         else:
             r_dev, p_dev = (reference.buf if isinstance(reference, DeviceFrames) else dev.upload_frames(reference)), None
-        outs = [dev.alloc(n * 8) if need else None
-                for need in (need_default, need_no_limiter, need_no_limiter_normalized)]
+        returned = (need_default, need_no_limiter, need_no_limiter_normalized)
+        cut = deliveries.needs() if deliveries else (False, False, False)
+        outs = [dev.alloc(n * 8) if need or extra else None for need, extra in zip(returned, cut)]
         try:
             route = {} if p_dev is None else {"profile": p_dev}
             report = dev.master(t_dev, n, r_dev, nr, native, *outs, fir=fir, **route)
@@ -109,19 +113,36 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                 debug(f"unlimited result normalised by {to_db(report.normalize_coefficient)} to reach the threshold")
             if need_default and not report.limiter_active:
                 debug("the result stays under the threshold: the limiter passes it through")
+            rate = config.internal_sample_rate
+            metered = {}                                         # rendering -> its measurement: one per rendering
             if loudness is not None:
-                rate = config.internal_sample_rate
                 loudness("target", dev.loudness(t_dev, n, rate))
                 if r_dev is not None:
                     loudness("reference", dev.loudness(r_dev, nr, rate))
-                for name, b in zip(("result", "result_no_limiter", "result_no_limiter_normalized"), outs):
-                    if b is not None:
-                        loudness(name, dev.loudness(b, n, rate))
+                for slot, name in enumerate(("result", "result_no_limiter", "result_no_limiter_normalized")):
+                    if returned[slot]:
+                        metered[slot] = dev.loudness(outs[slot], n, rate)
+                        loudness(name, metered[slot])
+            if deliveries:
+                from .delivery import DITHERS, SUBTYPE_BITS, delivery_gain
+
+                for key, slot, subtype, delivery in deliveries.items:
+                    if slot not in metered:
+                        metered[slot] = dev.loudness(outs[slot], n, rate)
+                    bits = SUBTYPE_BITS.get(subtype, 0)          # (float subtypes: float32 frames)
+                    record = delivery_gain(delivery, bits, metered[slot])
+                    deliveries.delivered[key] = record
+                    # queued behind the measurement; the array is valid after the one wait below
+                    deliveries.arrays[key] = dev.deliver(outs[slot], n, 2, record.gain, bits, DITHERS[delivery.dither],
+                                                         delivery.seed, wait=False)
+                    if loudness is not None:
+                        loudness("delivered:" + str(key), record)
             # queued one behind the other, then ONE wait; the arrays live in pinned host memory
             formats = encodings if encodings is not None else (None, None, None)
             pieces = []
             if preview is not None:
-                mastered = next(b for b in outs if b is not None)        # core.py:111: the first rendering there is
+                # core.py:111: the first rendering there is (one that only a delivery asked for comes last)
+                mastered = next((b for b, need in zip(outs, returned) if need), None) or next(b for b in outs if b is not None)
                 begin, size, fade = preview.plan(dev.window_energy(mastered, n, preview.size, preview.step), n)
                 for want, src, limit, fmt in ((preview.want_target, t_dev, preview.threshold, preview.encodings[0]),
                                               (preview.want_result, mastered, 0.0, preview.encodings[1])):
@@ -133,10 +154,10 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                         preview.target_piece = host
                     else:
                         preview.result_piece = host
-            results = tuple(None if b is None
+            results = tuple(None if not need
                             else dev.download(b, (n, 2), wait=False) if fmt is None
                             else dev.download_pcm(b, n, 2, PCM_BITS[fmt], wait=False)
-                            for b, fmt in zip(outs, formats))
+                            for b, fmt, need in zip(outs, formats, returned))
             dev.synchronize()
             for piece in pieces:
                 if piece is not None:
