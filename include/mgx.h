@@ -379,6 +379,55 @@ int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* m
 int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain, int32_t bits, int32_t dither,
                 uint64_t seed, void* out_dev);
 
+/* A true-peak look-ahead limiter for deliveries whose ceiling binds: where mgx_delivery_gain answers limited_by == 2 the
+ * linear policy leaves the file `shortfall_lu` under its target, and this is what makes up for it.  It is not the mastering
+ * limiter (mgx_limit: the reference's sample-peak limiter, part of the parity surface) and shares nothing with it: three
+ * launches per call, none of whose workgroups waits for another.  For x[n][2], pre-gain g > 0, linear ceiling c > 0,
+ * look-ahead L >= 1 frames and release R >= 0 frames, rho = exp(-1 / R) and rho = 0 at R = 0:
+ *   1. envelope   e[m] = g max over p = 0 .. 3 and both channels of |sum_j h[p + 4 j] x[m - j]|, h the meter's taps
+ *                 (mgx_loudness), frames outside the track zero: max_m e[m] / g is the meter's true peak of x.
+ *   2. reduction  d0[m] = 1 - c / e[m] where e[m] > c, else 0 (a NaN compares false: 0).
+ *   3. hold       d[m] = max of d0[m + j], |j| <= L, 0 <= m + j < n.
+ *   4. release    q[m] = max(d[m], rho q[m - 1]), q[-1] = 0.
+ *   5. smoothing  s[m] = sum_{|k| <= L} w[k] q[clamp(m + k, 0, n - 1)], w[k] = (L + 1 - |k|) / (L + 1)^2: two box-cars of
+ *                 L + 1 frames, weights >= 0 that sum to 1.  The edge frames are repeated, not padded with zeros.
+ *   6. output     out[m][ch] = (float)(((double)x[m][ch] g) (1 - s[m])), one gain for both channels; *max_reduction =
+ *                 max_m s[m].
+ * Guarantee: (1 - s[m]) e[m] <= c for every frame -- every q in the window of m is at least d there, and every d within L
+ * of m is at least d0[m].  Not guaranteed: that a meter reads `out` under c, because its interpolator sees 12 neighbouring
+ * frames with a gain each (the excess is about 1e-5 at L = 66, 2e-2 at L = 1).  A delivery therefore
+ * meters what the limiter made and trims it with mgx_delivery_gain, whose bound is the one that holds for the file.
+ * Float64 throughout, except that d0 crosses launches as float32 (rounded to nearest: 2^-25 on the gain); two calls give
+ * the same bytes.  Queued on the handle's stream; waits only when max_reduction (host, may be NULL) is asked for.  n == 0
+ * succeeds and launches nothing.  MGX_ERR_ARGUMENT, the message naming the field: a null handle, x_dev or out_dev; n < 0;
+ * out_dev overlapping x_dev; a pointer that is not 8-byte aligned; pre_gain or ceiling not finite or <= 0; lookahead
+ * outside [1, 2048]; release negative, not finite or above 2^22.  The handle is good for the next call. */
+int mgx_tp_limit(mgx_handle* h, const float* x_dev, int64_t n, double pre_gain, double ceiling, int32_t lookahead,
+                 double release, float* out_dev, double* max_reduction);
+/* The policy of a limited delivery, on the host; needs no GPU.  Called with the passes run so far -- their pre-gains in dB
+ * and the integrated loudness mgx_loudness read from each pass's output, passes == 0 before the first -- it says whether to
+ * run another pass, at which pre-gain, and the limiter's ceiling.  Every pass limits the ORIGINAL rendering.
+ *     ceiling   = 10^(ceiling_dbtp / 20) - A e / 2^(bits-1): the numerator of mgx_delivery_gain's g_peak
+ *     passes 0:   run only where mgx_delivery_gain(delivery, rendering) answers limited_by == 2;
+ *                 p_1 = target_lufs - rendering->integrated, 0 without a target or where that loudness is -infinity
+ *     passes k:   stop where there is no target, target - I_k <= tolerance_lu, k == max_passes, I_k is -infinity, or
+ *                 k >= 2 and (I_k - I_{k-1}) / (p_k - p_{k-1}) < 0.1 (a steady tone cannot be made louder under a ceiling);
+ *                 else p_{k+1} = p_k + (target - I_k) / slope, slope 1 after the first pass, then that quotient, at most 1
+ * When it answers run == 0 after k >= 1 passes the delivery is mgx_delivery_gain on the measurement of the last pass's
+ * output and mgx_deliver of that output: gain, head-room, shortfall_lu and the ceiling's proof are theirs.
+ * MGX_ERR_ARGUMENT: a null argument, a delivery without a ceiling or that mgx_delivery_gain refuses, max_passes outside
+ * [1, 16], passes outside [0, max_passes], tolerance_lu negative or not finite, NaN or +infinity among the passes. */
+#define MGX_LIMIT_PASSES_MAX 16
+typedef struct mgx_delivery_limit_plan {
+    double pre_gain_db;                  /* the next pass's pre-gain; with run == 0 the last pass's (0 before the first) */
+    double ceiling;                      /* linear */
+    int32_t run;                         /* 1: run a pass at pre_gain_db; 0: finish */
+    int32_t reserved;
+} mgx_delivery_limit_plan;
+int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_report* rendering, int32_t passes,
+                            const double* pre_gain_db, const double* integrated, int32_t max_passes, double tolerance_lu,
+                            mgx_delivery_limit_plan* next);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

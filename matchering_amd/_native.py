@@ -128,9 +128,21 @@ class MgxDeliveryResult(ctypes.Structure):
     ]
 
 
+class MgxDeliveryLimitPlan(ctypes.Structure):
+    """mgx_delivery_limit_plan (include/mgx.h)."""
+
+    _fields_ = [
+        ("pre_gain_db", ctypes.c_double),
+        ("ceiling", ctypes.c_double),
+        ("run", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
 PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
+LIMIT_PASSES_MAX = 16           # MGX_LIMIT_PASSES_MAX
 
 
 # every symbol include/mgx.h declares: name -> (restype, argtypes)
@@ -194,6 +206,11 @@ SYMBOLS = {
                                          ctypes.POINTER(MgxDeliveryResult)]),
     "mgx_deliver": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
                                    _VP]),
+    "mgx_tp_limit": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double,
+                                    _VP, c_double_p]),
+    "mgx_delivery_limit_step": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxLoudnessReport), ctypes.c_int32,
+                                               c_double_p, c_double_p, ctypes.c_int32, ctypes.c_double,
+                                               ctypes.POINTER(MgxDeliveryLimitPlan)]),
     "mgx_preview_cut": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_double, _VP]),
     "mgx_last_fir": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), c_int32_p]),

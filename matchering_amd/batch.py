@@ -28,7 +28,8 @@ and on a node with 8 GPUs::
 
 ``jobs.json`` is a list of ``{"target": path, "reference": path, "results": [{"file": path,
 "subtype": "PCM_16", "use_limiter": true, "normalize": true, "delivery": {"loudness": -14, "true_peak": -1,
-"dither": "tpdf_hp", "seed": 0}}, ...]}`` (``"delivery"`` and each of its keys optional: ``delivery.Delivery``); in place of ``"reference"`` a job may name a
+"dither": "tpdf_hp", "seed": 0, "limiter": true}}, ...]}`` (``"delivery"`` and each of its keys optional: ``delivery.Delivery``;
+``"limiter"``: ``true`` or the fields of ``delivery.TruePeakLimiter``); in place of ``"reference"`` a job may name a
 ``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
 list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).
 """

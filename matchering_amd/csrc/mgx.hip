@@ -30,6 +30,7 @@ static inline int roctxRangePop() { return 0; }
 #include "resample_kernel.h"
 #include "resample_plan.h"
 #include "deliver_kernel.h"            // (behind every other kernel: it moves none of them in the code object)
+#include "tp_limit_kernel.h"
 
 using namespace mgx;
 
@@ -154,6 +155,7 @@ struct mgx_handle {
     };
     std::map<int, LoudnessDev> loudness_plans;
     DevBuf loudness_out;                    // [nsub][2] sub-block energies, then [workgroups][2] peaks
+    DevBuf tp_plane, tp_words;              // mgx_tp_limit: the d0 plane [tiles * T] float32; aggregates and peaks, [2][tiles] float64
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // set by a kernel whose bounded wait expired (limiter look-back, level-correction round): one word of
@@ -1261,7 +1263,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false, const cha
 // ---------------------------------------------------------------------------
 extern "C" {
 
-int mgx_version(void) { return 105; }
+int mgx_version(void) { return 106; }
 const char* mgx_last_error(void) { return g_error.c_str(); }
 
 int mgx_device_count(int* count) {
@@ -1789,6 +1791,25 @@ static int deliver_format_check(int32_t bits, int32_t dither) {
     return 0;
 }
 
+// the numerator of g_peak: the linear ceiling less the quantiser's head-room (mgx_delivery_limit_step's ceiling is the same number)
+static int delivery_room(const mgx_delivery* delivery, double* room_out) {
+    // A: the most the meter's interpolator makes of errors of magnitude 1 -- the largest per-phase sum of |taps|
+    double taps[49], A = 0.0;
+    loudness_true_peak_taps(taps);
+    for (int p = 0; p < 4; ++p) {
+        double sum = 0.0;
+        for (int k = p; k < 49; k += 4) sum += std::fabs(taps[k]);
+        A = std::max(A, sum);
+    }
+    const double e = delivery->bits == 0 ? 0.0 : (delivery->dither ? 1.5 : 0.5);
+    const double margin = delivery->bits == 0 ? 0.0 : A * e / std::ldexp(1.0, delivery->bits - 1);
+    const double room = std::pow(10.0, delivery->ceiling_dbtp / 20.0) - margin;
+    if (!(room > 0.0))
+        return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: lower than the quantiser's own head-room at this width");
+    *room_out = room;
+    return 0;
+}
+
 int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* measured, mgx_delivery_result* result) {
     if (!delivery || !measured || !result) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(deliver_format_check(delivery->bits, delivery->dither));
@@ -1804,19 +1825,8 @@ int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* m
     const double g_loud = has_loud ? std::pow(10.0, (target - integrated) / 20.0) : 1.0;
     double g_peak = INFINITY;
     if (!std::isnan(ceiling)) {
-        // A: the most the meter's interpolator makes of errors of magnitude 1 -- the largest per-phase sum of |taps|
-        double taps[49], A = 0.0;
-        loudness_true_peak_taps(taps);
-        for (int p = 0; p < 4; ++p) {
-            double sum = 0.0;
-            for (int k = p; k < 49; k += 4) sum += std::fabs(taps[k]);
-            A = std::max(A, sum);
-        }
-        const double e = delivery->bits == 0 ? 0.0 : (delivery->dither ? 1.5 : 0.5);
-        const double margin = delivery->bits == 0 ? 0.0 : A * e / std::ldexp(1.0, delivery->bits - 1);
-        const double room = std::pow(10.0, ceiling / 20.0) - margin;
-        if (!(room > 0.0))
-            return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: lower than the quantiser's own head-room at this width");
+        double room;
+        MGX_TRY(delivery_room(delivery, &room));
         if (peak > 0.0) g_peak = room / peak;
     }
     const double gain = std::min(g_loud, g_peak);
@@ -1850,6 +1860,96 @@ int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain,
     a.out = out_dev;
     hipLaunchKernelGGL(k_deliver, dim3((unsigned)deliver_grid(samples)), dim3(DELIVER_THREADS), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_report* rendering, int32_t passes,
+                            const double* pre_gain_db, const double* integrated, int32_t max_passes, double tolerance_lu,
+                            mgx_delivery_limit_plan* next) {
+    if (!delivery || !rendering || !next) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (max_passes < 1 || max_passes > MGX_LIMIT_PASSES_MAX)
+        return fail(MGX_ERR_ARGUMENT, "max_passes: outside [1, " + std::to_string(MGX_LIMIT_PASSES_MAX) + "]");
+    if (!(tolerance_lu >= 0.0) || std::isinf(tolerance_lu)) return fail(MGX_ERR_ARGUMENT, "tolerance_lu: negative or not finite");
+    if (passes < 0 || passes > max_passes) return fail(MGX_ERR_ARGUMENT, "passes: outside [0, max_passes]");
+    if (passes > 0 && (!pre_gain_db || !integrated)) return fail(MGX_ERR_ARGUMENT, "pre_gain_db / integrated: null with passes run");
+    if (std::isnan(delivery->ceiling_dbtp)) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: a limiter needs a ceiling");
+    mgx_delivery_result linear;
+    MGX_TRY(mgx_delivery_gain(delivery, rendering, &linear));
+    next->run = 0;
+    next->reserved = 0;
+    next->pre_gain_db = passes > 0 ? pre_gain_db[passes - 1] : 0.0;
+    MGX_TRY(delivery_room(delivery, &next->ceiling));
+    const double target = delivery->target_lufs;
+    const bool has_target = !std::isnan(target) && std::isfinite(rendering->integrated);
+    if (passes == 0) {
+        if (linear.limited_by != 2) return 0;                  // the linear policy reaches what was asked for
+        next->run = 1;
+        next->pre_gain_db = has_target ? target - rendering->integrated : 0.0;
+        return 0;
+    }
+    const double p = pre_gain_db[passes - 1], loud = integrated[passes - 1];
+    if (std::isnan(p) || std::isnan(loud) || loud == INFINITY)
+        return fail(MGX_ERR_ARGUMENT, "pre_gain_db / integrated: NaN or +infinity in the passes run");
+    if (!has_target || target - loud <= tolerance_lu || passes == max_passes || std::isinf(loud)) return 0;
+    double slope = 1.0;
+    if (passes >= 2) {
+        const double dp = p - pre_gain_db[passes - 2], dl = loud - integrated[passes - 2];
+        if (dp == 0.0 || !(dl / dp >= 0.1)) return 0;           // more pre-gain buys no loudness: a steady tone under a ceiling
+        slope = std::min(dl / dp, 1.0);
+    }
+    next->run = 1;
+    next->pre_gain_db = p + (target - loud) / slope;
+    return 0;
+}
+
+int mgx_tp_limit(mgx_handle* h, const float* x_dev, int64_t n, double pre_gain, double ceiling, int32_t lookahead,
+                 double release, float* out_dev, double* max_reduction) {
+    // everything that depends on the numbers alone is settled before the handle is touched
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "n: negative");
+    if (!std::isfinite(pre_gain) || pre_gain <= 0.0) return fail(MGX_ERR_ARGUMENT, "pre_gain: must be finite and positive");
+    if (!std::isfinite(ceiling) || ceiling <= 0.0) return fail(MGX_ERR_ARGUMENT, "ceiling: must be finite and positive");
+    if (lookahead < 1 || lookahead > TPL_LOOKAHEAD_MAX)
+        return fail(MGX_ERR_ARGUMENT, "lookahead: outside [1, " + std::to_string(TPL_LOOKAHEAD_MAX) + "] frames");
+    if (!std::isfinite(release) || release < 0.0 || release > TPL_RELEASE_MAX)
+        return fail(MGX_ERR_ARGUMENT, "release: outside [0, 2^22] frames");
+    if (n > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_tp_limit: tracks of more than 500 million frames are not limited here");
+    if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
+    if (!x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
+    if (!out_dev) return fail(MGX_ERR_ARGUMENT, "out_dev: null");
+    if ((((size_t)x_dev) | ((size_t)out_dev)) & 7) return fail(MGX_ERR_ARGUMENT, "x_dev / out_dev: must be 8-byte aligned");
+    const char* xb = (const char*)x_dev;
+    const char* ob = (const char*)out_dev;
+    if (xb < ob + (size_t)n * 8 && ob < xb + (size_t)n * 8) return fail(MGX_ERR_ARGUMENT, "out_dev: overlaps x_dev");
+    if (max_reduction) *max_reduction = 0.0;
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    TpLimitArgs a;
+    double taps[49];
+    loudness_true_peak_taps(taps);
+    tpl_plan(a, n, pre_gain, ceiling, lookahead, release, taps);
+    MGX_TRY(ensure(h, h->tp_plane, (size_t)a.tiles * TPL_TILE * sizeof(float)));
+    MGX_TRY(ensure(h, h->tp_words, (size_t)a.tiles * 2 * sizeof(double)));
+    if (max_reduction) MGX_TRY(ensure_pinned(h, std::max((size_t)a.tiles * sizeof(double), (size_t)1 << 16)));
+    a.x = x_dev;
+    a.out = out_dev;
+    a.d0 = (float*)h->tp_plane.p;
+    a.agg = (double*)h->tp_words.p;
+    a.peak = a.agg + a.tiles;
+    const size_t region_a = tpl_region_a(lookahead), region_b = tpl_region_b(lookahead), lds = tpl_apply_lds_bytes(lookahead);
+    if (lds > LDS_PER_WORKGROUP_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_tp_limit: the look-ahead's window does not fit the LDS");
+    MGX_TRY(allow_lds(k_tp_apply, lds));
+    hipLaunchKernelGGL(k_tp_envelope, dim3((unsigned)a.tiles), dim3(TPL_THREADS), TPL_ENVELOPE_LDS_BYTES, h->stream, a);
+    if (a.tiles > 1)
+        hipLaunchKernelGGL(k_tp_aggregate, dim3((unsigned)(a.tiles - 1)), dim3(TPL_THREADS), TPL_AGGREGATE_LDS_BYTES, h->stream, a);
+    hipLaunchKernelGGL(k_tp_apply, dim3((unsigned)a.tiles), dim3(TPL_THREADS), lds, h->stream, a, (unsigned)region_a,
+                       (unsigned)region_b);
+    HIP_TRY(hipGetLastError());
+    if (!max_reduction) return 0;
+    HIP_TRY(hipMemcpyAsync(h->pinned, a.peak, (size_t)a.tiles * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(check_device_error(h));
+    const double* peaks = (const double*)h->pinned;
+    for (long long t = 0; t < a.tiles; ++t) *max_reduction = std::max(*max_reduction, peaks[t]);
     return 0;
 }
 

@@ -14,11 +14,18 @@ EBU R 128 normalisation is; never an approximation of a limiter -- and ``mgx_del
 packs in one pass.  The ceiling holds for the written file as a BS.1770 meter reads it back: the gain leaves the quantiser
 its head-room (include/mgx.h).  Where the ceiling keeps the loudness under the target the
 ``Delivered`` record says by how much (``shortfall_lu``).
+
+A delivery may carry a ``TruePeakLimiter``: where the ceiling binds -- and only there -- the rendering is first limited by
+``mgx_tp_limit``, a true-peak look-ahead limiter of its own (not the mastering limiter), in as many passes as
+``mgx_delivery_limit_step`` asks for; the linear policy above is then applied to the limited frames, so the ceiling's proof is
+unchanged and ``shortfall_lu`` says what is still missing.
+
+    mg.pcm16("club.wav", delivery=mg.Delivery(loudness=-9.0, true_peak=-1.0, dither="tpdf_hp", limiter=mg.TruePeakLimiter()))
 """
 
 import ctypes
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 
 from .loudness import Loudness, _db
 
@@ -27,16 +34,72 @@ SUBTYPE_BITS = {"PCM_16": 16, "PCM_24": 24, "PCM_32": 32}            # every oth
 LIMITED_BY = (None, "loudness", "true_peak")
 
 
+LOOKAHEAD_MAX = 2048                # frames: TPL_LOOKAHEAD_MAX (csrc/tp_limit_kernel.h)
+RELEASE_MAX = 2 ** 22               # frames
+PASSES_MAX = 16                     # MGX_LIMIT_PASSES_MAX
+
+
+@dataclass(frozen=True)
+class TruePeakLimiter:
+    """The limiter of a delivery whose ceiling binds (``mgx_tp_limit``).  ``lookahead_ms``: the look-ahead, the hold and
+    the length of each of the two smoothing box-cars; ``release_ms``: the time constant of the gain's exponential recovery;
+    ``max_passes``: the most passes the pre-gain is searched in; ``tolerance_lu``: the shortfall that ends the search."""
+
+    lookahead_ms: float = 1.5
+    release_ms: float = 50.0
+    max_passes: int = 4
+    tolerance_lu: float = 0.1
+
+    def __post_init__(self):
+        for name in ("lookahead_ms", "release_ms", "tolerance_lu"):
+            value = getattr(self, name)
+            if isinstance(value, bool) or not (isinstance(value, (int, float)) and math.isfinite(value)):
+                raise ValueError(f"TruePeakLimiter: {name} must be a finite number, got {value!r}")
+        if self.lookahead_ms <= 0.0:
+            raise ValueError(f"TruePeakLimiter: lookahead_ms must be positive, got {self.lookahead_ms!r}")
+        if self.release_ms < 0.0 or self.tolerance_lu < 0.0:
+            raise ValueError("TruePeakLimiter: release_ms and tolerance_lu must not be negative")
+        if isinstance(self.max_passes, bool) or not (isinstance(self.max_passes, int) and 1 <= self.max_passes <= PASSES_MAX):
+            raise ValueError(f"TruePeakLimiter: max_passes must be an integer in [1, {PASSES_MAX}], got {self.max_passes!r}")
+
+    def frames(self, rate):
+        """(L, R) at ``rate`` Hz: L = max(1, round(lookahead_ms rate / 1000)) frames, R = release_ms rate / 1000."""
+        lookahead = max(1, int(round(self.lookahead_ms * rate / 1000.0)))
+        release = self.release_ms * rate / 1000.0
+        if lookahead > LOOKAHEAD_MAX:
+            raise ValueError(f"TruePeakLimiter: lookahead_ms={self.lookahead_ms!r} is {lookahead} frames at {rate} Hz, "
+                             f"more than {LOOKAHEAD_MAX}")
+        if release > RELEASE_MAX:
+            raise ValueError(f"TruePeakLimiter: release_ms={self.release_ms!r} is more than {RELEASE_MAX} frames at {rate} Hz")
+        return lookahead, release
+
+    @classmethod
+    def from_json(cls, entry):
+        """``true`` for the defaults, or ``{"lookahead_ms": ..., "release_ms": ..., "max_passes": ..., "tolerance_lu": ...}``."""
+        if isinstance(entry, cls) or entry is None:
+            return entry
+        if entry is True:
+            return cls()
+        if not isinstance(entry, dict):
+            raise ValueError(f"a limiter is true or an object with lookahead_ms / release_ms / max_passes / tolerance_lu, got {entry!r}")
+        unknown = set(entry) - {f.name for f in fields(cls)}
+        if unknown:
+            raise ValueError(f"limiter: unknown keys {sorted(unknown)}")
+        return cls(**entry)
+
+
 @dataclass(frozen=True)
 class Delivery:
     """What a result is to meet.  ``loudness``: integrated loudness in LUFS, ``true_peak``: the ceiling in dBTP (at most
     0), either may be None; ``dither``: None, "tpdf" or "tpdf_hp" (high-passed TPDF), for 16 and 24-bit files;
-    ``seed``: the dither generator's key -- the same seed writes the same file."""
+    ``seed``: the dither generator's key -- the same seed writes the same file; ``limiter``: a ``TruePeakLimiter`` to run
+    where the ceiling keeps the linear gain under the target (it needs ``true_peak``), None for the linear gain alone."""
 
     loudness: float = None
     true_peak: float = None
     dither: str = None
     seed: int = 0
+    limiter: TruePeakLimiter = None
 
     def __post_init__(self):
         for name in ("loudness", "true_peak"):
@@ -49,6 +112,11 @@ class Delivery:
             raise ValueError(f"Delivery: dither must be None, 'tpdf' or 'tpdf_hp', got {self.dither!r}")
         if not (isinstance(self.seed, int) and 0 <= self.seed < 2 ** 64):
             raise ValueError(f"Delivery: seed must be an integer in [0, 2**64), got {self.seed!r}")
+        if self.limiter is not None:
+            if not isinstance(self.limiter, TruePeakLimiter):
+                raise ValueError(f"Delivery: limiter must be a TruePeakLimiter or None, got {self.limiter!r}")
+            if self.true_peak is None:
+                raise ValueError("Delivery: a limiter needs a true_peak ceiling to hold")
 
     def check_subtype(self, subtype):
         """The error ``Result`` raises at construction for a width this delivery cannot be written at."""
@@ -64,21 +132,27 @@ class Delivery:
 
     @classmethod
     def from_json(cls, entry):
-        """``{"loudness": ..., "true_peak": ..., "dither": ..., "seed": ...}`` of a batch job (every key optional)."""
+        """``{"loudness": ..., "true_peak": ..., "dither": ..., "seed": ..., "limiter": ...}`` of a batch job (every key
+        optional; ``"limiter"``: ``true`` for ``TruePeakLimiter()``, or an object with its fields)."""
         if isinstance(entry, cls):
             return entry
         if not isinstance(entry, dict):
-            raise ValueError(f"a delivery is an object with loudness / true_peak / dither / seed, got {entry!r}")
-        unknown = set(entry) - {"loudness", "true_peak", "dither", "seed"}
+            raise ValueError(f"a delivery is an object with loudness / true_peak / dither / seed / limiter, got {entry!r}")
+        unknown = set(entry) - {"loudness", "true_peak", "dither", "seed", "limiter"}
         if unknown:
             raise ValueError(f"delivery: unknown keys {sorted(unknown)}")
-        return cls(**entry)
+        if entry.get("limiter") in (None, False):
+            return cls(**{key: value for key, value in entry.items() if key != "limiter"})
+        return cls(**{**entry, "limiter": TruePeakLimiter.from_json(entry["limiter"])})
 
 
 @dataclass(frozen=True)
 class Delivered:
     """What became of one delivery: ``mgx_delivery_result``'s fields, the measurement they were derived from and the
-    request.  ``achieved_lufs`` / ``achieved_true_peak`` (linear) are predicted from the measurement of the rendering."""
+    request.  ``achieved_lufs`` / ``achieved_true_peak`` (linear) are predicted from the measurement of the rendering.
+    Where the delivery's limiter ran (``limiter_passes`` > 0) ``measured`` is still the rendering's measurement, ``limited``
+    the one of the last pass's frames -- which ``gain`` and the achieved values refer to -- ``pre_gain_db`` that pass's
+    pre-gain and ``max_reduction_db`` its deepest gain reduction (a negative number of dB)."""
 
     gain: float
     achieved_lufs: float
@@ -88,6 +162,10 @@ class Delivered:
     measured: Loudness
     delivery: Delivery
     bits: int
+    limiter_passes: int = 0         # 0: the limiter did not run
+    pre_gain_db: float = 0.0
+    max_reduction_db: float = 0.0
+    limited: Loudness = None
 
     @property
     def gain_db(self):
@@ -102,6 +180,9 @@ class Delivered:
         text = (f"gain {self.gain_db:+.2f} dB: {self.achieved_lufs:.2f} LUFS, true peak {self.achieved_true_peak_db:.2f} dBTP "
                 f"({'float32' if self.bits == 0 else f'{self.bits} bit'}"
                 f"{'' if self.delivery.dither is None else ', ' + self.delivery.dither})")
+        if self.limiter_passes > 0:
+            text += (f"; limited in {self.limiter_passes} pass{'' if self.limiter_passes == 1 else 'es'}: pre-gain "
+                     f"{self.pre_gain_db:+.2f} dB, at most {self.max_reduction_db:.2f} dB of reduction")
         if self.shortfall_lu > 0.0:
             text += f"; the ceiling keeps it {self.shortfall_lu:.2f} LU under the {self.delivery.loudness:g} LUFS target"
         return text
@@ -119,6 +200,32 @@ def delivery_gain(delivery: Delivery, bits: int, measured: Loudness) -> Delivere
                                                       ctypes.byref(out)))
     return Delivered(out.gain, out.achieved_lufs, out.achieved_true_peak, out.shortfall_lu, LIMITED_BY[out.limited_by],
                      measured, delivery, int(bits))
+
+
+def _report(measured):
+    from . import _native
+
+    report = _native.MgxLoudnessReport()
+    report.integrated, report.true_peak = measured.integrated, measured.true_peak
+    return report
+
+
+def limit_step(delivery: Delivery, bits: int, measured: Loudness, pre_gains_db=(), integrated=()):
+    """``mgx_delivery_limit_step`` (host only, needs no GPU): ``(run, pre_gain_db, ceiling)`` after the passes whose
+    pre-gains (dB) and integrated loudness are given -- none yet: whether the limiter is needed at all."""
+    from . import _native
+
+    if delivery.limiter is None:
+        raise ValueError("limit_step: the delivery carries no limiter")
+    passes = len(pre_gains_db)
+    if len(integrated) != passes:
+        raise ValueError("limit_step: one integrated loudness per pass")
+    array = ctypes.c_double * max(passes, 1)
+    plan = _native.MgxDeliveryLimitPlan()
+    _native.check(_native.library().mgx_delivery_limit_step(
+        ctypes.byref(delivery.native(bits)), ctypes.byref(_report(measured)), passes, array(*map(float, pre_gains_db)),
+        array(*map(float, integrated)), int(delivery.limiter.max_passes), float(delivery.limiter.tolerance_lu), ctypes.byref(plan)))
+    return bool(plan.run), plan.pre_gain_db, plan.ceiling
 
 
 RENDERINGS = ("result", "result_no_limiter", "result_no_limiter_normalized")

@@ -445,6 +445,26 @@ class Device:
             self.synchronize()
         return out
 
+    def tp_limit(self, buf, frames, pre_gain, ceiling, lookahead, release, out=None, reduction=True):
+        """The deliveries' true-peak look-ahead limiter on (frames, 2) float32 in HBM (``mgx_tp_limit``): pre-gain and
+        ceiling linear, look-ahead and release in frames.  Returns ``(out, max_reduction)``: the limited frames in a new
+        DeviceBuffer (or in ``out``) and the largest gain reduction s, for which the call waits; with ``reduction=False``
+        it is only queued and the second value is None."""
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        made = out if out is not None else DeviceBuffer(self, max(int(frames) * 8, 1))
+        worst = ctypes.c_double()
+        try:
+            check(library().mgx_tp_limit(self.handle, ctypes.c_void_p(ptr), int(frames), float(pre_gain), float(ceiling),
+                                         int(lookahead), float(release), ctypes.c_void_p(made.ptr),
+                                         ctypes.byref(worst) if reduction else None))
+        except Exception:
+            if out is None:
+                made.release()
+            raise
+        if reduction:
+            self._keep_until_sync.clear()      # (the call has waited for the stream)
+        return made, (worst.value if reduction else None)
+
     # ---- previews on frames that are still in HBM (mgx_window_energy / mgx_preview_cut) ----------
     def window_energy(self, buf, frames, size, step):
         """dsp.py:128-143: sum of squares (both channels) of every window of ``size`` frames every ``step``."""

@@ -44,6 +44,36 @@ def _is_profile(reference):
     return isinstance(reference, ReferenceProfile)
 
 
+def _limited(dev, rendering, n, rate, delivery, bits, measured):
+    """The passes of a delivery's limiter (``mgx_tp_limit``, each from the rendering itself, each metered) as
+    ``mgx_delivery_limit_step`` asks for them: ``(Delivered, the last pass's frames)``, or None where it asks for none.
+    The record is ``mgx_delivery_gain``'s on the measurement of those frames."""
+    from dataclasses import replace
+
+    from .delivery import delivery_gain, limit_step
+
+    lookahead, release = delivery.limiter.frames(rate)
+    pre, loud, scratch, reading, worst = [], [], None, None, 0.0
+    try:
+        while True:
+            run, pre_gain_db, ceiling = limit_step(delivery, bits, measured, pre, loud)
+            if not run:
+                break
+            scratch, worst = dev.tp_limit(rendering, n, 10.0 ** (pre_gain_db / 20.0), ceiling, lookahead, release, out=scratch)
+            reading = dev.loudness(scratch, n, rate)
+            pre.append(pre_gain_db)
+            loud.append(reading.integrated)
+        if not pre:
+            return None
+        record = replace(delivery_gain(delivery, bits, reading), measured=measured, limiter_passes=len(pre), pre_gain_db=pre[-1],
+                         max_reduction_db=20.0 * float(np.log10(1.0 - worst)), limited=reading)
+    except Exception:
+        if scratch is not None:
+            scratch.release()
+        raise
+    return record, scratch
+
+
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
          encodings=None, preview=None, loudness=None, deliveries=None):
@@ -62,7 +92,8 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # (mgx_loudness), before any encoding; None: nothing is measured.  ``deliveries``: a delivery.DeliveryRequest --
     # renditions of the renderings at a loudness target, under a true-peak ceiling, dithered (mgx_delivery_gain,
     # mgx_deliver), made while the renderings are still in HBM and left in the request; a rendering that only a delivery
-    # names is computed but not returned, and ``loudness`` also receives ("delivered:" + key, delivery.Delivered).)
+    # names is computed but not returned, and ``loudness`` also receives ("delivered:" + key, delivery.Delivered).  A
+    # delivery that carries a limiter and whose ceiling binds is limited first (mgx_tp_limit, mgx_delivery_limit_step).)
     dev = device if device is not None else default_device()
     target = _as_frames(target, "target")
     profile = reference if _is_profile(reference) else None
@@ -130,11 +161,22 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                     if slot not in metered:
                         metered[slot] = dev.loudness(outs[slot], n, rate)
                     bits = SUBTYPE_BITS.get(subtype, 0)          # (float subtypes: float32 frames)
-                    record = delivery_gain(delivery, bits, metered[slot])
+                    limited = None
+                    if delivery.limiter is not None:
+                        # (None where the ceiling does not bind: the delivery then takes the route of one without a limiter)
+                        limited = _limited(dev, outs[slot], n, rate, delivery, bits, metered[slot])
+                    if limited is None:
+                        record, frames = delivery_gain(delivery, bits, metered[slot]), outs[slot]
+                    else:
+                        record, frames = limited
                     deliveries.delivered[key] = record
                     # queued behind the measurement; the array is valid after the one wait below
-                    deliveries.arrays[key] = dev.deliver(outs[slot], n, 2, record.gain, bits, DITHERS[delivery.dither],
-                                                         delivery.seed, wait=False)
+                    try:
+                        deliveries.arrays[key] = dev.deliver(frames, n, 2, record.gain, bits, DITHERS[delivery.dither],
+                                                             delivery.seed, wait=False)
+                    finally:
+                        if limited is not None:
+                            frames.release() # (recycled by later work on this stream only, which is ordered behind the kernel)
                     if loudness is not None:
                         loudness("delivered:" + str(key), record)
             # queued one behind the other, then ONE wait; the arrays live in pinned host memory
