@@ -14,8 +14,14 @@
  *    except through the handle.
  *  - every function returns 0 on success, a negative mgx_status otherwise;
  *    mgx_last_error() gives the message (thread-local).
- *  - a handle is bound to one GPU and one HIP stream; calls on one handle are
- *    serialised by the caller, different handles are independent.
+ *  - a handle is bound to one GPU and one HIP stream ("the handle's stream" below);
+ *    calls on one handle are serialised by the caller, different handles are
+ *    independent.  Work takes effect in the order of the calls.  Behind that order
+ *    the analysis and FIR design of an mgx_master call may run on a second stream
+ *    of the handle's, under the previous call's convolution and limiter, where it
+ *    reads nothing a call before it writes; mgx_synchronize and every other call
+ *    that waits for the stream wait for that work too.  Only a handle that is
+ *    its device's only live handle does this.
  */
 #ifndef MGX_H
 #define MGX_H
@@ -473,7 +479,10 @@ int mgx_code_bytes(int32_t* bytes, int32_t capacity);
 
 /* Device address of the FIR pair ([2][fft_size] float32: mid taps then side taps, level gain
  * not included) designed by the last mgx_master / uploaded by the last mgx_convolve on this
- * handle -- the payload of the RCCL exchange below. */
+ * handle -- the payload of the RCCL exchange below.  The address is good until the next mgx_master* or
+ * mgx_convolve call on the handle: a handle keeps two such tables and consecutive calls may use them in
+ * turn, so a later call's FIR need not appear behind an address obtained earlier.  Copy the table out
+ * (or pass the address as fir_dev to the very next call) and ask again after every call. */
 int mgx_last_fir(mgx_handle* h, void** taps_dev, int32_t* taps);
 
 /* ---- multi-GPU: one process per GPU, FIR taps over RCCL/xGMI ---------------- */

@@ -8,7 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmgx.so")
 SOURCES = [os.path.join(CSRC, "mgx.hip"), os.path.join(CSRC, "fir_design.cpp"), os.path.join(CSRC, "fir_plan.cpp"),
-           os.path.join(CSRC, "resample_plan.cpp"), os.path.join(CSRC, "loudness_plan.cpp")]
+           os.path.join(CSRC, "resample_plan.cpp"), os.path.join(CSRC, "loudness_plan.cpp"),
+           os.path.join(CSRC, "call_pipeline.cpp")]
 
 
 def _deps():

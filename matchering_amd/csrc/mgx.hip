@@ -20,6 +20,7 @@ static inline int roctxRangePop() { return 0; }
 #include <vector>
 
 #include "../../include/mgx.h"
+#include "call_pipeline.h"
 #include "code_sizes.h"
 #include "fir_design.h"
 #include "fir_plan.h"
@@ -122,24 +123,37 @@ struct LimiterChain {
 };
 static LimiterChain g_limiter_chain[MAX_DEVICES];
 
+// What the front half of a master call (analysis, FIR design, filter spectra) writes and its back half reads.  A
+// handle owns CALL_CONTEXTS of them, so that the next call's front half can run under this call's back half
+// (call_pipeline.h); everything only back halves touch stays single in the handle.
+struct CallContext {
+    TrackWork track[2];
+    DevBuf fir_scratch, scalars, taps, filt, cstate;
+    DevBuf fir_robust;                      // lowess_it > 0: robustness weights and residuals, [2][2][nlog]
+    int last_taps = 0;
+};
+
 struct mgx_handle {
     int device = 0;
     int cus = 0;                            // compute units of the device (read at mgx_create)
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;           // main: everything but a pipelined call's front half
+    hipStream_t front = nullptr;            // the front halves of pipelined master calls (call_pipeline.h)
+    hipStream_t fq = nullptr;               // where the front-half runners queue: `stream`, or `front` inside a pipelined call
+    CallPipeline pipe;
+    CallContext ctx[CALL_CONTEXTS];         // a pipelined call takes the other one; the stage-level entry points use the most recent call's
+    hipEvent_t front_done[CALL_CONTEXTS] = {}, back_done[CALL_CONTEXTS] = {};
+    hipEvent_t main_now = nullptr;          // wait (b): recorded on main when a dirty call's front half starts
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool stage_timing = false;                                    // mgx_stage_timing
     hipEvent_t stage_ev[MGX_STAGE_COUNT][2] = {};
     bool stage_used[MGX_STAGE_COUNT] = {};
     std::map<int, float2*> twiddles;
-    TrackWork track[2];
-    DevBuf y, mid, block_peak, filt, taps, partial, cstate, scalars, conv_queue;
+    DevBuf y, mid, block_peak, partial, conv_queue;
     DevBuf lim_published, lim_ctrl, lim_weights, round_ctr, tail_gains, band, band_info;
     std::vector<double> lim_weights_host;
     DevBuf peak_words;                      // mgx_peak_count: {bits of the maximum, count}
-    DevBuf fir_robust;                      // lowess_it > 0: robustness weights and residuals, [2][2][nlog]
     DevBuf lim_tables;                      // general filter orders: matrix powers and look-back matrices
     std::vector<double> lim_tables_host;
-    DevBuf fir_scratch;
     // mgx_resample: the weights of every rate pair this handle has converted, designed and uploaded once
     struct ResampleDev {
         std::shared_ptr<const ResamplePlan> plan;
@@ -164,7 +178,6 @@ struct mgx_handle {
     bool limiter_ran_by_number = false;      // a limiter launch since the last error check dealt chunks by workgroup number
     int* error_host = nullptr;
     int* error_dev = nullptr;
-    int last_taps = 0;
     // the arguments of the last mgx_master call, kept so that it can be queued again when the level-correction
     // tail reports that its workgroups were not resident together (check_device_error)
     struct MasterCall {
@@ -194,10 +207,43 @@ struct mgx_handle {
     bool fir_round4 = false;                // MGX_FIR_ROUND4=1: the dense operator at 16384 taps, the chain itself beyond
 };
 
+static CallContext& context(mgx_handle* h) { return h->ctx[h->pipe.current()]; }
+
+// both streams idle.  Main first: it waits for every front half that has its back half queued; then whatever front half
+// is still being queued.
+static int drain(mgx_handle* h) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->front) HIP_TRY(hipStreamSynchronize(h->front));
+    return 0;
+}
+// What an entry point does where it waits for its work: synchronising main drains the front stream too, because every
+// front half is followed by a back half on main that waits for it (master_impl drains both where queueing failed half-way)
+static int sync_main(mgx_handle* h) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->pipe.drained();
+    return 0;
+}
+
+// The front stream and the events of the call pipeline, made when a handle first finds itself alone on its device: the
+// lanes of a batch never pipeline (master_impl) and keep their one stream.  The lowest priority: where both streams have
+// work the dispatcher takes the back half's, which the caller is waiting for, and the front half fills what that leaves
+// idle (at default priority most of the gain is lost).
+static int ensure_front(mgx_handle* h) {
+    if (h->front) return 0;
+    int least = 0, greatest = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    for (hipEvent_t* e : {&h->front_done[0], &h->front_done[1], &h->back_done[0], &h->back_done[1], &h->main_now})
+        HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    HIP_TRY(hipStreamCreateWithPriority(&h->front, hipStreamNonBlocking, least));
+    // (no back_done was recorded behind the calls so far: the first front half waits for everything main holds instead)
+    h->pipe.other_work();
+    return 0;
+}
+
 static int ensure(mgx_handle* h, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return 0;
     if (b.p) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        MGX_TRY(drain(h));
         HIP_TRY(hipFree(b.p));
         b.p = nullptr;
         b.bytes = 0;
@@ -210,7 +256,7 @@ static int ensure(mgx_handle* h, DevBuf& b, size_t bytes) {
 static int ensure_pinned(mgx_handle* h, size_t bytes) {
     if (h->pinned_bytes >= bytes) return 0;
     if (h->pinned) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        MGX_TRY(drain(h));
         HIP_TRY(hipHostFree(h->pinned));
         h->pinned = nullptr;
         h->pinned_bytes = 0;
@@ -254,7 +300,7 @@ struct StageScope {
 static int ensure_ctrl(mgx_handle* h);
 // one stages.main: every launch queued on the handle's stream (check_device_error may queue the last call again), and
 // the boundary around it
-static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c);
+static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const MasterPlan& plan);
 static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
                        int64_t n_reference, const mgx_profile_header* profile, const mgx_config* cfg,
                        const float* fir_given, float* result_dev, float* result_no_limiter_dev,
@@ -324,7 +370,7 @@ static int check_length(long long n) {
 }
 
 // ---------------------------------------------------------------------------
-// stage runners (asynchronous on h->stream)
+// stage runners (asynchronous: the front-half runners on h->fq, the others on h->stream)
 // ---------------------------------------------------------------------------
 // workgroups of k_analyze<log2f> one CU holds (LDS and wave slots)
 static int analysis_workgroups_per_cu(int log2f) {
@@ -348,7 +394,7 @@ static int launch_analysis(mgx_handle* h, void (*kernel)(AnalysisArgs, AnalysisA
                            const AnalysisArgs& a1, int nwg0, int nwg) {
     const size_t lds = analysis_lds_bytes<LOG2N>();
     MGX_TRY(allow_lds(kernel, lds));
-    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(Fft2<LOG2N>::T), lds, h->stream, a0, a1, nwg0);
+    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(Fft2<LOG2N>::T), lds, h->fq, a0, a1, nwg0);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -439,7 +485,7 @@ static int run_analysis(mgx_handle* h, const mgx_config* cfg, const float* x0, l
     if (w1) MGX_TRY(analysis_args(h, x1, n1, cfg, *w1, a1));
     const int nwg = w0.nwg + (w1 ? w1->nwg : 0);
     switch (ilog2_exact(cfg->fft_size)) {
-#define SMALL(L) case L: hipLaunchKernelGGL(k_analyze_small<L>, dim3(nwg), dim3(256), 0, h->stream, a0, a1, w0.nwg); HIP_TRY(hipGetLastError()); break;
+#define SMALL(L) case L: hipLaunchKernelGGL(k_analyze_small<L>, dim3(nwg), dim3(256), 0, h->fq, a0, a1, w0.nwg); HIP_TRY(hipGetLastError()); break;
         SMALL(3) SMALL(4) SMALL(5)
 #undef SMALL
 #define CASE(L) case L: MGX_TRY(launch_analysis<L>(h, k_analyze<L>, a0, a1, w0.nwg, nwg)); break;
@@ -484,16 +530,16 @@ static int run_levels(mgx_handle* h, const mgx_config* cfg, TrackWork* first, Tr
     for (TrackWork* w : {first, second})
         if (w) MGX_TRY(ensure(h, w->part, (size_t)SPEC_SLICES * 2 * (half + 1) * sizeof(double)));
     const LevelsArgs l0 = levels_args(*first), l1 = second ? levels_args(*second) : l0;
-    hipLaunchKernelGGL(k_levels, dim3(tracks), dim3(1024), lds, h->stream, l0, l1, cfg->threshold, cfg->min_value);
+    hipLaunchKernelGGL(k_levels, dim3(tracks), dim3(1024), lds, h->fq, l0, l1, cfg->threshold, cfg->min_value);
     const SpectraArgs s0 = spectra_args(*first), s1 = second ? spectra_args(*second) : s0;
-    hipLaunchKernelGGL(k_average_spectra, dim3((half + 1 + 63) / 64, 2, SPEC_SLICES * tracks), dim3(1024), 0, h->stream,
+    hipLaunchKernelGGL(k_average_spectra, dim3((half + 1 + 63) / 64, 2, SPEC_SLICES * tracks), dim3(1024), 0, h->fq,
                        s0, s1, half + 1);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-// device-side FIR design (fir_plan.h): spectra partial sums of both tracks -> h->taps ([2][F] float),
-// level gain c0 -> h->scalars[0].  No host synchronisation.  The chain raw -> smooth is one dense
+// device-side FIR design (fir_plan.h): spectra partial sums of both tracks -> cx.taps ([2][F] float),
+// level gain c0 -> cx.scalars[0].  No host synchronisation.  The chain raw -> smooth is one dense
 // operator per plan (fir_kernels.h), built on first use.
 static int build_fir_operator(mgx_handle* h, const FirPlanView& pl, double** out, int2** band_out) {
     const size_t per = (size_t)3 * pl.bins + (size_t)3 * pl.nlog + pl.lw.anchors;
@@ -505,17 +551,17 @@ static int build_fir_operator(mgx_handle* h, const FirPlanView& pl, double** out
     const size_t lds_scan = (size_t)FirDesign::Scan::SCRATCH * sizeof(Affine);
     for (int col0 = 0; col0 < pl.bins; col0 += batch) {
         const int nb = std::min(batch, pl.bins - col0);
-        hipLaunchKernelGGL(k_fir_unit_a, dim3(nb), dim3(1024), lds_scan, h->stream, pl, scratch, col0);
-        hipLaunchKernelGGL(k_fir_lowess, dim3((pl.lw.anchors + 15) / 16, nb), dim3(1024), 0, h->stream, pl, scratch);
-        hipLaunchKernelGGL(k_fir_b, dim3(nb), dim3(1024), lds_scan, h->stream, pl, scratch);
-        hipLaunchKernelGGL(k_fir_gather, dim3((nb + 255) / 256, pl.bins), dim3(256), 0, h->stream, pl, scratch, col0,
+        hipLaunchKernelGGL(k_fir_unit_a, dim3(nb), dim3(1024), lds_scan, h->fq, pl, scratch, col0);
+        hipLaunchKernelGGL(k_fir_lowess, dim3((pl.lw.anchors + 15) / 16, nb), dim3(1024), 0, h->fq, pl, scratch);
+        hipLaunchKernelGGL(k_fir_b, dim3(nb), dim3(1024), lds_scan, h->fq, pl, scratch);
+        hipLaunchKernelGGL(k_fir_gather, dim3((nb + 255) / 256, pl.bins), dim3(256), 0, h->fq, pl, scratch, col0,
                            nb, M);
     }
     int2* band = nullptr;
     HIP_TRY(hipMalloc((void**)&band, (size_t)pl.bins * sizeof(int2)));
-    hipLaunchKernelGGL(k_fir_band, dim3(pl.bins), dim3(256), 0, h->stream, (const double*)M, pl.bins, band);
+    hipLaunchKernelGGL(k_fir_band, dim3(pl.bins), dim3(256), 0, h->fq, (const double*)M, pl.bins, band);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->fq));
     HIP_TRY(hipFree(scratch));
     *out = M;
     *band_out = band;
@@ -529,11 +575,11 @@ static int pack_fir_factor(mgx_handle* h, double* dense, int rows, int cols, Pla
     DevBuf band_tmp;
     HIP_TRY(hipMalloc(&band_tmp.p, (size_t)rows * sizeof(int2)));
     int2* band_dev = (int2*)band_tmp.p;
-    hipLaunchKernelGGL(k_fir_band, dim3(rows), dim3(256), 0, h->stream, (const double*)dense, cols, band_dev);
+    hipLaunchKernelGGL(k_fir_band, dim3(rows), dim3(256), 0, h->fq, (const double*)dense, cols, band_dev);
     HIP_TRY(hipGetLastError());
     std::vector<int2> band(rows);
-    HIP_TRY(hipMemcpyAsync(band.data(), band_dev, (size_t)rows * sizeof(int2), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(band.data(), band_dev, (size_t)rows * sizeof(int2), hipMemcpyDeviceToHost, h->fq));
+    HIP_TRY(hipStreamSynchronize(h->fq));
     std::vector<FactorRow> desc(rows);
     long long total = 0;
     for (int r = 0; r < rows; ++r) {
@@ -543,12 +589,12 @@ static int pack_fir_factor(mgx_handle* h, double* dense, int rows, int cols, Pla
     f.bytes = (size_t)std::max<long long>(total, 2) * sizeof(double);
     HIP_TRY(hipMalloc((void**)&f.rows, (size_t)rows * sizeof(FactorRow)));
     HIP_TRY(hipMalloc((void**)&f.packed, f.bytes));
-    HIP_TRY(hipMemcpyAsync(f.rows, desc.data(), (size_t)rows * sizeof(FactorRow), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(f.packed, 0, f.bytes, h->stream));
-    hipLaunchKernelGGL(k_fir_pack, dim3(rows), dim3(256), 0, h->stream, (const double*)dense, cols, (const FactorRow*)f.rows,
+    HIP_TRY(hipMemcpyAsync(f.rows, desc.data(), (size_t)rows * sizeof(FactorRow), hipMemcpyHostToDevice, h->fq));
+    HIP_TRY(hipMemsetAsync(f.packed, 0, f.bytes, h->fq));
+    hipLaunchKernelGGL(k_fir_pack, dim3(rows), dim3(256), 0, h->fq, (const double*)dense, cols, (const FactorRow*)f.rows,
                        f.packed);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->fq));
     return 0;
 }
 
@@ -566,9 +612,9 @@ static int build_fir_factors(mgx_handle* h, const FirPlanView& pl, PlanDev& pd) 
     double* dense = (double*)dense_tmp.p;
     for (int col0 = 0; col0 < pl.bins; col0 += batch) {
         const int nb = std::min(batch, pl.bins - col0);
-        hipLaunchKernelGGL(k_fir_unit_a, dim3(nb), dim3(1024), lds_scan, h->stream, pl, scratch, col0);
-        hipLaunchKernelGGL(k_fir_lowess, dim3((anchors + 15) / 16, nb), dim3(1024), 0, h->stream, pl, scratch);
-        hipLaunchKernelGGL(k_fir_gather_plane, dim3((nb + 255) / 256, anchors), dim3(256), 0, h->stream, pl, scratch, col0,
+        hipLaunchKernelGGL(k_fir_unit_a, dim3(nb), dim3(1024), lds_scan, h->fq, pl, scratch, col0);
+        hipLaunchKernelGGL(k_fir_lowess, dim3((anchors + 15) / 16, nb), dim3(1024), 0, h->fq, pl, scratch);
+        hipLaunchKernelGGL(k_fir_gather_plane, dim3((nb + 255) / 256, anchors), dim3(256), 0, h->fq, pl, scratch, col0,
                            nb, pl.bins, 1, dense);
     }
     HIP_TRY(hipGetLastError());
@@ -576,9 +622,9 @@ static int build_fir_factors(mgx_handle* h, const FirPlanView& pl, PlanDev& pd) 
     // B: unit fits -> the smooth curve on the linear grid (the same bytes: bins x anchors)
     for (int col0 = 0; col0 < anchors; col0 += batch) {
         const int nb = std::min(batch, anchors - col0);
-        hipLaunchKernelGGL(k_fir_unit_fit, dim3(nb), dim3(256), 0, h->stream, pl, scratch, col0);
-        hipLaunchKernelGGL(k_fir_b, dim3(nb), dim3(1024), lds_scan, h->stream, pl, scratch);
-        hipLaunchKernelGGL(k_fir_gather_plane, dim3((nb + 255) / 256, pl.bins), dim3(256), 0, h->stream, pl, scratch, col0,
+        hipLaunchKernelGGL(k_fir_unit_fit, dim3(nb), dim3(256), 0, h->fq, pl, scratch, col0);
+        hipLaunchKernelGGL(k_fir_b, dim3(nb), dim3(1024), lds_scan, h->fq, pl, scratch);
+        hipLaunchKernelGGL(k_fir_gather_plane, dim3((nb + 255) / 256, pl.bins), dim3(256), 0, h->fq, pl, scratch, col0,
                            nb, anchors, 0, dense);
     }
     HIP_TRY(hipGetLastError());
@@ -595,6 +641,7 @@ static ProfileWant profile_want(const mgx_config* cfg) {
 // k_average_spectra on the target and k_profile_raw.  Leaves what the pair route's curve kernels leave.
 static int run_profile_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanView& pl, const TrackWork& tw,
                              const mgx_profile_header* profile, double* raw) {
+    CallContext& cx = context(h);
     const ProfileWant want = profile_want(cfg);
     const size_t lds_curve = profile_curve_lds_bytes(tw.divisions, tw.nwg);
     if (lds_curve <= LDS_PER_WORKGROUP_MAX) {
@@ -604,15 +651,15 @@ static int run_profile_curve(mgx_handle* h, const mgx_config* cfg, const FirPlan
         const int tile = rounds(33) < rounds(32) ? 33 : 32;
         const auto curve = tile == 33 ? k_profile_curve<33> : k_profile_curve<32>;
         MGX_TRY(allow_lds(curve, lds_curve));
-        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->stream, ct, profile, want,
-                           pl.bins, pl.fft, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)h->scalars.p,
-                           (CorrectionState*)h->cstate.p, h->error_dev);
+        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->fq, ct, profile, want,
+                           pl.bins, pl.fft, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)cx.scalars.p,
+                           (CorrectionState*)cx.cstate.p, h->error_dev);
     } else {
         TrackWork& t = const_cast<TrackWork&>(tw);
         MGX_TRY(run_levels(h, cfg, &t, nullptr));
-        hipLaunchKernelGGL(k_profile_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->stream, pl,
+        hipLaunchKernelGGL(k_profile_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->fq, pl,
                            (const double*)tw.part.p, (const TrackStats*)tw.stats.p, tw.segs_per_piece, profile, want,
-                           cfg->min_value, raw, (double*)h->scalars.p, (CorrectionState*)h->cstate.p, h->error_dev);
+                           cfg->min_value, raw, (double*)cx.scalars.p, (CorrectionState*)cx.cstate.p, h->error_dev);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -622,6 +669,7 @@ static int run_profile_curve(mgx_handle* h, const mgx_config* cfg, const FirPlan
 // the piece tables fit a workgroup's LDS (always, short of thousands of pieces), three otherwise.
 static int run_pair_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanView& pl, const TrackWork& tw,
                           const TrackWork& rw, double* raw) {
+    CallContext& cx = context(h);
     const int max_div = std::max(tw.divisions, rw.divisions);
     const size_t lds_curve = match_curve_lds_bytes(max_div, tw.nwg + rw.nwg);
     if (lds_curve <= LDS_PER_WORKGROUP_MAX) {
@@ -632,9 +680,9 @@ static int run_pair_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanVie
         const int tile = rounds(33) < rounds(32) ? 33 : 32;
         const auto curve = tile == 33 ? k_match_curve<33> : k_match_curve<32>;
         MGX_TRY(allow_lds(curve, lds_curve));
-        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->stream, ct, cr, pl.bins,
-                           pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)h->scalars.p,
-                           (CorrectionState*)h->cstate.p, h->error_dev);
+        hipLaunchKernelGGL(curve, dim3((pl.bins + tile - 1) / tile, 2), dim3(1024), lds_curve, h->fq, ct, cr, pl.bins,
+                           pl.fft, max_div, cfg->threshold, cfg->min_value, pl.min_value, raw, (double*)cx.scalars.p,
+                           (CorrectionState*)cx.cstate.p, h->error_dev);
     } else {
         TrackWork& t = const_cast<TrackWork&>(tw);
         TrackWork& r = const_cast<TrackWork&>(rw);
@@ -647,8 +695,8 @@ static int run_pair_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanVie
         in.segs_t = tw.segs_per_piece;
         in.segs_r = rw.segs_per_piece;
         in.eps = cfg->min_value;
-        hipLaunchKernelGGL(k_fir_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->stream, pl, in, raw,
-                           (double*)h->scalars.p, (CorrectionState*)h->cstate.p);
+        hipLaunchKernelGGL(k_fir_raw, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->fq, pl, in, raw,
+                           (double*)cx.scalars.p, (CorrectionState*)cx.cstate.p);
     }
     return 0;
 }
@@ -657,6 +705,7 @@ static int run_pair_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanVie
 // (then `rw` is not looked at), or null
 static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const TrackWork& rw,
                           const float* fir_given, const mgx_profile_header* profile = nullptr) {
+    CallContext& cx = context(h);
     FirDesignParams p{cfg->fft_size, cfg->internal_sample_rate, cfg->lin_log_oversampling, cfg->lowess_frac,
                       cfg->lowess_it, cfg->lowess_delta, cfg->min_value};
     std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(p);
@@ -699,47 +748,47 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     const FirPlanView pl = plan->view(pd.blob);
     const size_t per = (size_t)3 * pl.bins + (size_t)3 * pl.nlog + pl.lw.anchors;
     // (two scratch planes, the raw curves, and the partial transforms of the tap synthesis: [2][fft/2] double2)
-    MGX_TRY(ensure(h, h->fir_scratch, (2 * per + 2 * (size_t)pl.bins + 2 * (size_t)pl.fft + 2) * sizeof(double)));
-    MGX_TRY(ensure(h, h->scalars, 64));
-    MGX_TRY(ensure(h, h->taps, (size_t)2 * cfg->fft_size * sizeof(float)));
-    double* scratch = (double*)h->fir_scratch.p;
+    MGX_TRY(ensure(h, cx.fir_scratch, (2 * per + 2 * (size_t)pl.bins + 2 * (size_t)pl.fft + 2) * sizeof(double)));
+    MGX_TRY(ensure(h, cx.scalars, 64));
+    MGX_TRY(ensure(h, cx.taps, (size_t)2 * cfg->fft_size * sizeof(float)));
+    double* scratch = (double*)cx.fir_scratch.p;
     double* raw = scratch + 2 * per;
-    MGX_TRY(ensure(h, h->cstate, sizeof(CorrectionState)));
+    MGX_TRY(ensure(h, cx.cstate, sizeof(CorrectionState)));
     if (profile)
         MGX_TRY(run_profile_curve(h, cfg, pl, tw, profile, raw));
     else
         MGX_TRY(run_pair_curve(h, cfg, pl, tw, rw, raw));
     if (fir_given) {             // the levels above are this pair's own; the matching EQ is somebody else's
-        if (fir_given != (const float*)h->taps.p)
-            HIP_TRY(hipMemcpyAsync(h->taps.p, fir_given, (size_t)2 * cfg->fft_size * sizeof(float),
-                                   hipMemcpyDeviceToDevice, h->stream));
-        h->last_taps = cfg->fft_size;
+        if (fir_given != (const float*)cx.taps.p)
+            HIP_TRY(hipMemcpyAsync(cx.taps.p, fir_given, (size_t)2 * cfg->fft_size * sizeof(float),
+                                   hipMemcpyDeviceToDevice, h->fq));
+        cx.last_taps = cfg->fft_size;
         return 0;
     }
     if (direct) {
         const size_t lds_scan = (size_t)FirDesign::Scan::SCRATCH * sizeof(Affine);
-        hipLaunchKernelGGL(k_fir_direct_a, dim3(2), dim3(1024), lds_scan, h->stream, pl, scratch, (const double*)raw);
+        hipLaunchKernelGGL(k_fir_direct_a, dim3(2), dim3(1024), lds_scan, h->fq, pl, scratch, (const double*)raw);
         if (robust) {
-            MGX_TRY(ensure(h, h->fir_robust, (size_t)4 * pl.nlog * sizeof(double)));
-            hipLaunchKernelGGL(k_fir_lowess_robust, dim3(2), dim3(1024), 0, h->stream, pl, scratch,
-                               (double*)h->fir_robust.p, cfg->lowess_it);
+            MGX_TRY(ensure(h, cx.fir_robust, (size_t)4 * pl.nlog * sizeof(double)));
+            hipLaunchKernelGGL(k_fir_lowess_robust, dim3(2), dim3(1024), 0, h->fq, pl, scratch,
+                               (double*)cx.fir_robust.p, cfg->lowess_it);
         } else {
-            hipLaunchKernelGGL(k_fir_lowess, dim3((pl.lw.anchors + 15) / 16, 2), dim3(1024), 0, h->stream, pl, scratch);
+            hipLaunchKernelGGL(k_fir_lowess, dim3((pl.lw.anchors + 15) / 16, 2), dim3(1024), 0, h->fq, pl, scratch);
         }
-        hipLaunchKernelGGL(k_fir_b, dim3(2), dim3(1024), lds_scan, h->stream, pl, scratch);
+        hipLaunchKernelGGL(k_fir_b, dim3(2), dim3(1024), lds_scan, h->fq, pl, scratch);
     } else if (factored) {
-        hipLaunchKernelGGL(k_fir_apply_a, dim3(pl.lw.anchors), dim3(256), 0, h->stream, pl, (const double*)pd.A.packed,
+        hipLaunchKernelGGL(k_fir_apply_a, dim3(pl.lw.anchors), dim3(256), 0, h->fq, pl, (const double*)pd.A.packed,
                            (const FactorRow*)pd.A.rows, (const double*)raw, scratch);
-        hipLaunchKernelGGL(k_fir_apply_b, dim3((pl.bins + 255) / 256), dim3(256), 0, h->stream, pl, (const double*)pd.B.packed,
+        hipLaunchKernelGGL(k_fir_apply_b, dim3((pl.bins + 255) / 256), dim3(256), 0, h->fq, pl, (const double*)pd.B.packed,
                            (const FactorRow*)pd.B.rows, (const double*)raw, scratch);
     } else {
-        hipLaunchKernelGGL(k_fir_matvec, dim3(pl.bins), dim3(256), 0, h->stream, pl, (const double*)pd.M,
+        hipLaunchKernelGGL(k_fir_matvec, dim3(pl.bins), dim3(256), 0, h->fq, pl, (const double*)pd.M,
                            (const int2*)pd.band, (const double*)raw, scratch);
     }
     if (pl.fft < 64) {                                          // 8 .. 32 taps: the plain cosine sum, one thread per tap
-        hipLaunchKernelGGL(k_fir_taps_direct, dim3(2), dim3(1024), 0, h->stream, pl, (const double*)scratch, (float*)h->taps.p);
+        hipLaunchKernelGGL(k_fir_taps_direct, dim3(2), dim3(1024), 0, h->fq, pl, (const double*)scratch, (float*)cx.taps.p);
         HIP_TRY(hipGetLastError());
-        h->last_taps = cfg->fft_size;
+        cx.last_taps = cfg->fft_size;
         return 0;
     }
     // tap synthesis: the symmetric cosine sum up to 4096 taps (8 us in one launch -- two launches of the split
@@ -755,23 +804,23 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
         switch (m) {
 #define MGX_TAPS_SUB(L)                                                                                                \
     case 1 << L:                                                                                                       \
-        hipLaunchKernelGGL(k_fir_taps_sub<L>, dim3(split, 2), dim3(TapFft<L>::T), lds_sub, h->stream, pl,              \
+        hipLaunchKernelGGL(k_fir_taps_sub<L>, dim3(split, 2), dim3(TapFft<L>::T), lds_sub, h->fq, pl,              \
                            (const double*)scratch, sub);                                                               \
         break;
             MGX_TAPS_SUB(9) MGX_TAPS_SUB(10) MGX_TAPS_SUB(11)
 #undef MGX_TAPS_SUB
             default: return fail(MGX_ERR_UNSUPPORTED, "tap synthesis: transform length not instantiated");
         }
-        hipLaunchKernelGGL(k_fir_taps_combine, dim3((pl.fft / 2 + 255) / 256, 2), dim3(256), 0, h->stream, pl,
-                           (const double2*)sub, split, (float*)h->taps.p);
+        hipLaunchKernelGGL(k_fir_taps_combine, dim3((pl.fft / 2 + 255) / 256, 2), dim3(256), 0, h->fq, pl,
+                           (const double2*)sub, split, (float*)cx.taps.p);
     } else {
         const size_t lds_taps = ((size_t)pl.bins + 2048 + 2 * TAP_ROWS) * sizeof(double);
         MGX_TRY(allow_lds(k_fir_taps, lds_taps));
-        hipLaunchKernelGGL(k_fir_taps, dim3((pl.fft / 4 + 1 + TAP_ROWS - 1) / TAP_ROWS, 2), dim3(1024), lds_taps, h->stream,
-                           pl, (const double*)scratch, (float*)h->taps.p);
+        hipLaunchKernelGGL(k_fir_taps, dim3((pl.fft / 4 + 1 + TAP_ROWS - 1) / TAP_ROWS, 2), dim3(1024), lds_taps, h->fq,
+                           pl, (const double*)scratch, (float*)cx.taps.p);
     }
     HIP_TRY(hipGetLastError());
-    h->last_taps = cfg->fft_size;
+    cx.last_taps = cfg->fft_size;
     return 0;
 }
 
@@ -786,12 +835,16 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
 //   CONV_WIDE:  k_conv_wide<LOG2N>, F taps on N = 4F (conv_wide_kernel.h; F = 4096 on N = 16384); blocks of 3N/4
 //               frames, one per workgroup, dealt round-robin
 enum ConvForm { CONV_QUEUE, CONV_DELAY, CONV_WIDE };
+// The two launches of a convolution can be queued apart: the filter spectra belong to a master call's front half (on
+// h->fq), the main kernel to its back half (on h->stream).
+enum ConvPhases { CONV_SPECTRA = 1, CONV_MAIN = 2, CONV_BOTH = 3 };
 
 // *blocks: the number of blocks, one peak each in h->block_peak
 template <int LOG2N, ConvForm FORM, bool MULTI = false>
 static int launch_conv(mgx_handle* h, Conv2Args a, const float* taps_dev, double gain, const double* gain_ptr,
-                       long long* blocks) {
+                       long long* blocks, int phases) {
     using F = Fft2<LOG2N>;
+    CallContext& cx = context(h);
     const size_t lds = conv_lds_bytes<LOG2N>();
     void (*kernel)(Conv2Args);
     long long hop;                                              // input frames from one block to the next
@@ -805,23 +858,24 @@ static int launch_conv(mgx_handle* h, Conv2Args a, const float* taps_dev, double
         kernel = k_conv_wide<LOG2N>;
         hop = ConvWide<LOG2N>::HOP;
     }
-    if constexpr (FORM == CONV_WIDE) {
-        MGX_TRY(allow_lds(k_conv_wide_prep<LOG2N>, lds));
-    } else {
-        MGX_TRY(allow_lds(k_conv_prep<LOG2N>, lds));
-    }
-    MGX_TRY(allow_lds(kernel, lds));
-    {
+    if (phases & CONV_SPECTRA) {
+        if constexpr (FORM == CONV_WIDE) {
+            MGX_TRY(allow_lds(k_conv_wide_prep<LOG2N>, lds));
+        } else {
+            MGX_TRY(allow_lds(k_conv_prep<LOG2N>, lds));
+        }
         StageScope scope(h, MGX_STAGE_FILTER_SPECTRA);
         if constexpr (FORM == CONV_WIDE) {
-            hipLaunchKernelGGL(k_conv_wide_prep<LOG2N>, dim3(2), dim3(F::T), lds, h->stream, taps_dev, a.tw,
-                               (float2*)h->filt.p, gain_ptr, gain);
+            hipLaunchKernelGGL(k_conv_wide_prep<LOG2N>, dim3(2), dim3(F::T), lds, h->fq, taps_dev, a.tw,
+                               (float2*)cx.filt.p, gain_ptr, gain);
         } else {
-            hipLaunchKernelGGL(k_conv_prep<LOG2N>, dim3(2 * a.parts), dim3(F::T), lds, h->stream, taps_dev, a.tw,
-                               (float2*)h->filt.p, a.parts, gain_ptr, gain);
+            hipLaunchKernelGGL(k_conv_prep<LOG2N>, dim3(2 * a.parts), dim3(F::T), lds, h->fq, taps_dev, a.tw,
+                               (float2*)cx.filt.p, a.parts, gain_ptr, gain);
         }
     }
     HIP_TRY(hipGetLastError());
+    if (!(phases & CONV_MAIN)) return 0;
+    MGX_TRY(allow_lds(kernel, lds));
     a.npairs = (a.n + hop - 1) / hop;
     MGX_TRY(ensure(h, h->block_peak, (size_t)a.npairs * sizeof(float)));
     a.pair_peak = (float*)h->block_peak.p;
@@ -858,11 +912,14 @@ static int launch_conv(mgx_handle* h, Conv2Args a, const float* taps_dev, double
 constexpr int LONG_FIR_LOG2N = 14;
 constexpr int WIDE_LOG2N = 14;                                  // CONV_WIDE: 4096 taps on 16384-point blocks
 static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const float* taps_dev, double gain,
-                    float* y, float* ymid, long long* npairs_out, const double* gain_ptr = nullptr) {
+                    float* y, float* ymid, long long* npairs_out, const double* gain_ptr = nullptr,
+                    int phases = CONV_BOTH) {
+    CallContext& cx = context(h);
     const int l = ilog2_exact(taps);
     if (l < 0) return fail(MGX_ERR_ARGUMENT, "FIR length must be a power of two");
     MGX_TRY(check_length(n));
     if (taps <= CONV_DIRECT_MAX_TAPS) {                          // 2 .. 32 taps: in the time domain (small_fft_kernels.h)
+        if (!(phases & CONV_MAIN)) return 0;                     // (no filter spectra)
         const long long tiles = (n + CONV_DIRECT_TILE - 1) / CONV_DIRECT_TILE;
         MGX_TRY(ensure(h, h->block_peak, (size_t)tiles * sizeof(float)));
         if (npairs_out) *npairs_out = tiles;
@@ -880,28 +937,28 @@ static int run_conv(mgx_handle* h, const float* x, long long n, int taps, const 
     const int log2b = wide ? WIDE_LOG2N : std::min(l + 1, LONG_FIR_LOG2N);
     const size_t nb = (size_t)1 << log2b;
     const int parts = wide ? 1 : (int)((size_t)2 * taps / nb);
-    MGX_TRY(ensure(h, h->filt, 2 * (size_t)parts * nb * sizeof(float2)));
+    MGX_TRY(ensure(h, cx.filt, 2 * (size_t)parts * nb * sizeof(float2)));
     Conv2Args a;
     a.x = reinterpret_cast<const float2*>(x);
     a.n = n;
     a.y = reinterpret_cast<float2*>(y);
     a.ymid = ymid;
-    a.h_mid = (const float2*)h->filt.p;
-    a.h_side = (const float2*)h->filt.p + (size_t)parts * nb;
+    a.h_mid = (const float2*)cx.filt.p;
+    a.h_side = (const float2*)cx.filt.p + (size_t)parts * nb;
     a.parts = parts;
     a.queue = nullptr;
     a.run = 0;
     MGX_TRY(get_twiddles(h, log2b, &a.tw));
     long long blocks = 0;
     if (wide) {
-        MGX_TRY((launch_conv<WIDE_LOG2N, CONV_WIDE>(h, a, taps_dev, gain, gain_ptr, &blocks)));
+        MGX_TRY((launch_conv<WIDE_LOG2N, CONV_WIDE>(h, a, taps_dev, gain, gain_ptr, &blocks, phases)));
     } else if (parts == 2 && !h->no_conv_delay) {
-        MGX_TRY((launch_conv<LONG_FIR_LOG2N, CONV_DELAY>(h, a, taps_dev, gain, gain_ptr, &blocks)));
+        MGX_TRY((launch_conv<LONG_FIR_LOG2N, CONV_DELAY>(h, a, taps_dev, gain, gain_ptr, &blocks, phases)));
     } else if (parts > 1) {
-        MGX_TRY((launch_conv<LONG_FIR_LOG2N, CONV_QUEUE, true>(h, a, taps_dev, gain, gain_ptr, &blocks)));
+        MGX_TRY((launch_conv<LONG_FIR_LOG2N, CONV_QUEUE, true>(h, a, taps_dev, gain, gain_ptr, &blocks, phases)));
     } else {
         switch (log2b) {
-#define CASE(L) case L: MGX_TRY((launch_conv<L, CONV_QUEUE>(h, a, taps_dev, gain, gain_ptr, &blocks))); break;
+#define CASE(L) case L: MGX_TRY((launch_conv<L, CONV_QUEUE>(h, a, taps_dev, gain, gain_ptr, &blocks, phases))); break;
             CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14)
 #undef CASE
             default: return fail(MGX_ERR_UNSUPPORTED, "FIR length not supported by the convolution kernel");
@@ -948,7 +1005,7 @@ static const char* const TOO_MANY_PIECES = "too many analysis pieces for the lev
 // (the reference's TrackStats, or a profile's header).
 static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const double* reference_match_rms,
                           long long n_target, long long nblocks, const LimiterParams* lp, bool* limiter_preset) {
-    CorrectionState* cs = (CorrectionState*)h->cstate.p;
+    CorrectionState* cs = (CorrectionState*)context(h).cstate.p;
     RoundArgs ra;
     ra.mid = (const float*)h->mid.p;
     ra.piece = tw.piece;
@@ -1195,7 +1252,7 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false, const cha
     if (h->round_ctr.p) HIP_TRY(hipMemsetAsync(h->round_ctr.p, 0, h->round_ctr.bytes, h->stream));
     if (h->lim_ctrl.p) HIP_TRY(hipMemsetAsync(h->lim_ctrl.p, 0, 64, h->stream));
     if (h->conv_queue.p) HIP_TRY(hipMemsetAsync(h->conv_queue.p, 0, 64, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     if (what & DEVICE_ERROR_PROFILE) {
         // (before the input report: a profile that was not read makes no statement about anybody's samples)
         // (k_profile_merge: the verdict in the low byte, the refused source's position + 1 above it)
@@ -1231,8 +1288,9 @@ static int check_device_error(mgx_handle* h, bool may_requeue = false, const cha
         if (lookback_new) h->limiter_tickets = true;
         if (may_requeue && h->last_call.valid && outstanding == 1 && copies == 0) {
             const mgx_handle::MasterCall again = h->last_call;
-            MGX_TRY(queue_master(h, again));
-            HIP_TRY(hipStreamSynchronize(h->stream));
+            MGX_TRY(drain(h));                                  // (serial replay: both streams idle, then main alone)
+            MGX_TRY(queue_master(h, again, h->pipe.replay()));
+            MGX_TRY(sync_main(h));
             h->masters_outstanding = 0;
             bool clean = true;
             for (int i = 0; i < DEVICE_ERROR_SLOTS; ++i) clean = clean && e[i] == 0;
@@ -1336,6 +1394,7 @@ int mgx_create(int device, mgx_handle** out) {
     h->fir_round4 = env_flag("MGX_FIR_ROUND4");
     h->avoid_tail = env_flag("MGX_NO_TAIL");
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->fq = h->stream;
     HIP_TRY(hipEventCreate(&h->ev0));
     HIP_TRY(hipEventCreate(&h->ev1));
     HIP_TRY(hipEventCreateWithFlags(&h->lim_done, hipEventDisableTiming));
@@ -1366,7 +1425,7 @@ int mgx_create(int device, mgx_handle** out) {
 int mgx_destroy(mgx_handle* h) {
     if (!h) return 0;
     hipSetDevice(h->device);
-    hipStreamSynchronize(h->stream);
+    drain(h);
     {
         LimiterChain& chain = g_limiter_chain[h->device % MAX_DEVICES];
         std::lock_guard<std::mutex> lock(chain.mu);
@@ -1383,6 +1442,9 @@ int mgx_destroy(mgx_handle* h) {
     for (auto& pair : h->stage_ev)
         for (hipEvent_t e : pair)
             if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {h->front_done[0], h->front_done[1], h->back_done[0], h->back_done[1], h->main_now})
+        if (e) hipEventDestroy(e);
+    if (h->front) hipStreamDestroy(h->front);
     hipStreamDestroy(h->stream);
     delete h;                               // (and with it every DevBuf of the handle and its tracks)
     return 0;
@@ -1397,25 +1459,27 @@ int mgx_malloc(mgx_handle* h, size_t bytes, void** dev) {
 int mgx_free(mgx_handle* h, void* dev) {
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
     if (!dev) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(drain(h));
+    h->pipe.drained();
     HIP_TRY(hipFree(dev));
     h->last_call.valid = false;             // (its pointers may be the block that has just gone: never queued again)
     return 0;
 }
 int mgx_memcpy_h2d(mgx_handle* h, void* dev, const void* host, size_t bytes) {
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
+    h->pipe.other_work();
     HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     return 0;
 }
 int mgx_memcpy_d2h(mgx_handle* h, void* host, const void* dev, size_t bytes) {
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
     HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     MGX_TRY(check_device_error(h, true));
     if (h->requeued) {                       // the copy above took the failed run's bytes: take them again
         HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        MGX_TRY(sync_main(h));
     }
     return 0;
 }
@@ -1432,18 +1496,23 @@ int mgx_host_free(void* host) {
 }
 int mgx_memcpy_h2d_async(mgx_handle* h, void* dev, const void* host, size_t bytes) {
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
+    h->pipe.other_work();
     HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 int mgx_memcpy_d2h_async(mgx_handle* h, void* host, const void* dev, size_t bytes) {
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
+    // (a download writes no device memory and does not hold the next front half back -- unless it reads a context's own
+    // taps, mgx_last_fir's pointer, which the front half of the call after next writes)
+    for (const CallContext& cx : h->ctx)
+        if (overlap(byte_range(dev, bytes), byte_range(cx.taps.p, cx.taps.bytes))) h->pipe.other_work();
     HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
     if (h->masters_outstanding > 0) ++h->downloads_outstanding;
     return 0;
 }
 int mgx_synchronize(mgx_handle* h) {
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     return check_device_error(h, true);
 }
 int mgx_timer_start(mgx_handle* h) {
@@ -1466,7 +1535,8 @@ int mgx_analyze(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* 
     if (!h || !x_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(check_config(cfg));
     HIP_TRY(hipSetDevice(h->device));
-    TrackWork& w = h->track[is_reference ? 1 : 0];
+    h->pipe.other_work();
+    TrackWork& w = context(h).track[is_reference ? 1 : 0];
     w.is_reference = is_reference;
     MGX_TRY(run_analysis(h, cfg, x_dev, n, w));
     MGX_TRY(run_levels(h, cfg, &w, nullptr));
@@ -1479,7 +1549,7 @@ int mgx_analyze(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* 
     }
     TrackStats st;
     HIP_TRY(hipMemcpyAsync(&st, w.stats.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     const int half = cfg->fft_size / 2;
     if (peak) *peak = st.peak;
     if (amplitude_coefficient) *amplitude_coefficient = st.amplitude_c;
@@ -1506,15 +1576,16 @@ int mgx_design_fir(const mgx_config* cfg, const double* avg_target, const double
 }
 
 static int upload_taps(mgx_handle* h, const double* fir_mid, const double* fir_side, int taps) {
-    MGX_TRY(ensure(h, h->taps, (size_t)2 * taps * sizeof(float)));
+    CallContext& cx = context(h);
+    MGX_TRY(ensure(h, cx.taps, (size_t)2 * taps * sizeof(float)));
     MGX_TRY(ensure_pinned(h, std::max((size_t)2 * taps * sizeof(float), (size_t)1 << 16)));
     float* st = (float*)h->pinned;
     for (int i = 0; i < taps; ++i) {
         st[i] = (float)fir_mid[i];
         st[taps + i] = (float)fir_side[i];
     }
-    HIP_TRY(hipMemcpyAsync(h->taps.p, st, (size_t)2 * taps * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    h->last_taps = taps;
+    HIP_TRY(hipMemcpyAsync(cx.taps.p, st, (size_t)2 * taps * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    cx.last_taps = taps;
     return 0;
 }
 
@@ -1523,10 +1594,11 @@ int mgx_convolve(mgx_handle* h, const float* x_dev, int64_t n, const double* fir
     if (!h || !x_dev || !fir_mid || !fir_side || !y_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
     if (n <= 0) return fail(MGX_ERR_ARGUMENT, "empty input");
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     MGX_TRY(upload_taps(h, fir_mid, fir_side, taps));
     long long nblocks = 0;
-    MGX_TRY(run_conv(h, x_dev, n, taps, (const float*)h->taps.p, gain, y_dev, y_mid_dev, &nblocks));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(run_conv(h, x_dev, n, taps, (const float*)context(h).taps.p, gain, y_dev, y_mid_dev, &nblocks));
+    MGX_TRY(sync_main(h));
     if (peak) {
         std::vector<float> bp(nblocks);
         HIP_TRY(hipMemcpy(bp.data(), h->block_peak.p, nblocks * sizeof(float), hipMemcpyDeviceToHost));
@@ -1543,11 +1615,12 @@ int mgx_clipped_piece_sumsq(mgx_handle* h, const float* mid_dev, int64_t n, int6
     if (piece_size <= 0 || divisions <= 0 || piece_size * divisions > n)
         return fail(MGX_ERR_ARGUMENT, "piece grid does not fit the array");
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     int chunks = 0;
     MGX_TRY(run_clipped_sumsq(h, mid_dev, piece_size, divisions, nullptr, gain, &chunks));
     std::vector<double> part((size_t)divisions * chunks);
     HIP_TRY(hipMemcpyAsync(part.data(), h->partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     for (int d = 0; d < divisions; ++d) {
         double s = 0.0;
         for (int c = 0; c < chunks; ++c) s += part[(size_t)d * chunks + c];
@@ -1561,11 +1634,13 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
     if (!h || !x_dev || !out_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(check_config(cfg));
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
+    CallContext& cx = context(h);
     // peak -> early-out decision, through the same kernels the pipeline uses
-    MGX_TRY(ensure(h, h->cstate, sizeof(CorrectionState)));
-    MGX_TRY(ensure(h, h->scalars, 64));
+    MGX_TRY(ensure(h, cx.cstate, sizeof(CorrectionState)));
+    MGX_TRY(ensure(h, cx.scalars, 64));
     MGX_TRY(ensure_pinned(h, 1 << 16));
-    CorrectionState* cs = (CorrectionState*)h->cstate.p;
+    CorrectionState* cs = (CorrectionState*)cx.cstate.p;
     hipLaunchKernelGGL(k_correction_init, dim3(1), dim3(1), 0, h->stream, cs, gain);
     // per-block peaks of x via the scale kernel's sibling: reuse k_finalize on a peak pass
     const long long nb = (n + 4095) / 4096;
@@ -1576,12 +1651,12 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
                        cfg->threshold, cfg->min_value, cs);
     double* post = (double*)h->pinned;
     *post = post_gain;
-    HIP_TRY(hipMemcpyAsync(h->scalars.p, post, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(cx.scalars.p, post, sizeof(double), hipMemcpyHostToDevice, h->stream));
     CorrectionState host_cs;
     // Error words that earlier asynchronous mgx_master calls may have left are THEIRS: looked at (and reported) before
     // this call queues anything, so that the retry below can only ever answer for this call's own limiter.
     if (h->masters_outstanding > 0) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        MGX_TRY(sync_main(h));
         MGX_TRY(check_device_error(h));
     }
     LimiterParams lp;
@@ -1589,10 +1664,10 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
     if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     for (int attempt = 0;; ++attempt) {
         const bool tickets_before = h->limiter_tickets;
-        MGX_TRY(run_limiter(h, x_dev, n, lp, cfg->threshold, &cs->gain, (const double*)h->scalars.p, &cs->limiter_active,
+        MGX_TRY(run_limiter(h, x_dev, n, lp, cfg->threshold, &cs->gain, (const double*)cx.scalars.p, &cs->limiter_active,
                             out_dev));
         HIP_TRY(hipMemcpyAsync(&host_cs, cs, sizeof(host_cs), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        MGX_TRY(sync_main(h));
         const int rc = check_device_error(h);
         if (rc == 0) break;
         if (attempt > 0 || tickets_before || !h->limiter_tickets) return rc;       // (once more when the handle has just switched to tickets)
@@ -1606,6 +1681,7 @@ int mgx_scale(mgx_handle* h, const float* x_dev, int64_t n, double gain, float* 
     if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
     if (n == 0) return 0;                                       // nothing to scale: a success that launches nothing
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(k_scale_outputs, dim3(grid), dim3(256), 0, h->stream, (const float2*)x_dev, (long long)n,
                        (const double*)nullptr, gain, (const double*)nullptr, (float2*)out_dev, (float2*)nullptr);
@@ -1616,6 +1692,7 @@ int mgx_scale(mgx_handle* h, const float* x_dev, int64_t n, double gain, float* 
 int mgx_peak_count(mgx_handle* h, const float* x_dev, int64_t samples, double* peak, int64_t* count) {
     if (!h || !x_dev || !peak || !count) return fail(MGX_ERR_ARGUMENT, "null argument");
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     MGX_TRY(ensure(h, h->peak_words, 64));
     MGX_TRY(ensure_pinned(h, (size_t)1 << 16));
     unsigned long long* words = (unsigned long long*)h->peak_words.p;
@@ -1628,7 +1705,7 @@ int mgx_peak_count(mgx_handle* h, const float* x_dev, int64_t samples, double* p
     }
     unsigned long long* host = (unsigned long long*)h->pinned;
     HIP_TRY(hipMemcpyAsync(host, words, 16, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     const unsigned bits = (unsigned)host[0];
     float f;
     std::memcpy(&f, &bits, 4);
@@ -1673,6 +1750,7 @@ int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_ra
         return 0;
     }
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     mgx_handle::LoudnessDev& dev = h->loudness_plans[sample_rate];
     if (!dev.table.p) {
         dev.plan = loudness_design(sample_rate);
@@ -1701,7 +1779,7 @@ int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_ra
     hipLaunchKernelGGL(k_loudness, dim3((unsigned)g.workgroups), dim3(LOUD_THREADS), LOUD_LDS_BYTES, h->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h->pinned, h->loudness_out.p, doubles * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     // (as every blocking call: this also takes whatever the calls queued before it have reported, and with it the
     // handle's count of mgx_master calls and downloads outstanding -- nothing of theirs can be queued again from here)
     MGX_TRY(check_device_error(h, false, "the frames to measure"));
@@ -1721,6 +1799,7 @@ int mgx_window_energy(mgx_handle* h, const float* x_dev, int64_t n, int64_t size
     if (!h || !x_dev || !energy || !count || n < 1 || size < 1 || step < 1)
         return fail(MGX_ERR_ARGUMENT, "bad window energy arguments");
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     if (size > n) size = n;                                   // dsp.py:131-132: the whole array is the only window
     const int64_t windows = (n - size) / step + 1;
     *count = windows;
@@ -1736,7 +1815,7 @@ int mgx_window_energy(mgx_handle* h, const float* x_dev, int64_t n, int64_t size
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h->pinned, h->partial.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     MGX_TRY(check_device_error(h));
     const double* part = (const double*)h->pinned;
     for (int64_t w = 0; w < windows; ++w) {
@@ -1752,6 +1831,7 @@ int mgx_preview_cut(mgx_handle* h, const float* x_dev, int64_t n, int64_t begin,
     if (!h || !x_dev || !out_dev || begin < 0 || size < 1 || begin + size > n || fade < 0 || fade > size)
         return fail(MGX_ERR_ARGUMENT, "bad preview cut arguments");
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     const unsigned grid = (unsigned)std::min<int64_t>((size + 255) / 256, 4096);
     hipLaunchKernelGGL(k_preview_cut, dim3(grid), dim3(256), 0, h->stream, (const float2*)x_dev, (long long)begin,
                        (long long)size, (long long)fade, clip_limit, (float2*)out_dev);
@@ -1764,6 +1844,7 @@ int mgx_pcm_decode(mgx_handle* h, const void* pcm_dev, int64_t samples, int32_t 
     if (bits != 16 && bits != 24 && bits != 32) return fail(MGX_ERR_ARGUMENT, "PCM width must be 16, 24 or 32 bits");
     if (samples <= 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 8192);
     hipLaunchKernelGGL(k_pcm_decode, dim3(grid), dim3(256), 0, h->stream, pcm_dev, (long long)samples, bits, out_dev);
     HIP_TRY(hipGetLastError());
@@ -1775,6 +1856,7 @@ int mgx_pcm_encode(mgx_handle* h, const float* x_dev, int64_t samples, int32_t b
     if (bits != 16 && bits != 24 && bits != 32) return fail(MGX_ERR_ARGUMENT, "PCM width must be 16, 24 or 32 bits");
     if (samples <= 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 8192);
     hipLaunchKernelGGL(k_pcm_encode, dim3(grid), dim3(256), 0, h->stream, x_dev, (long long)samples, bits, pcm_dev);
     HIP_TRY(hipGetLastError());
@@ -1849,6 +1931,7 @@ int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain,
     if ((((size_t)x_dev) | ((size_t)out_dev)) & 15) return fail(MGX_ERR_ARGUMENT, "x_dev / out_dev: must be 16-byte aligned");
     if (samples == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     DeliverArgs a;
     a.x = x_dev;
     a.samples = samples;
@@ -1923,6 +2006,7 @@ int mgx_tp_limit(mgx_handle* h, const float* x_dev, int64_t n, double pre_gain, 
     if (max_reduction) *max_reduction = 0.0;
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     TpLimitArgs a;
     double taps[49];
     loudness_true_peak_taps(taps);
@@ -1946,7 +2030,7 @@ int mgx_tp_limit(mgx_handle* h, const float* x_dev, int64_t n, double pre_gain, 
     HIP_TRY(hipGetLastError());
     if (!max_reduction) return 0;
     HIP_TRY(hipMemcpyAsync(h->pinned, a.peak, (size_t)a.tiles * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     MGX_TRY(check_device_error(h));
     const double* peaks = (const double*)h->pinned;
     for (long long t = 0; t < a.tiles; ++t) *max_reduction = std::max(*max_reduction, peaks[t]);
@@ -1974,6 +2058,7 @@ int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels,
     if (out_capacity_frames < frames) return fail(MGX_ERR_ARGUMENT, "the output holds fewer frames than the conversion gives");
     if (frames == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     mgx_handle::ResampleDev& dev = h->resample_plans[{rate_in, rate_out}];
     if (!dev.matrix.p) {
         dev.plan = resample_design(rate_in, rate_out);
@@ -2017,8 +2102,9 @@ int mgx_resample_plan(mgx_handle* h, int32_t rate_in, int32_t rate_out, void** w
 
 // ---- the boundary: stages.main ----------------------------------------------
 } // extern "C"
-// every launch of one stages.main, queued on the handle's stream (no host round trip)
-static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
+// every launch of one stages.main (no host round trip): the front half on main or, for a pipelined call, on the
+// front stream behind the waits `plan` asks for; the back half on main
+static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const MasterPlan& plan) {
     const float* target_dev = c.target;
     const float* reference_dev = c.reference;
     const float* fir_given = c.fir_given;
@@ -2029,9 +2115,23 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     float* result_no_limiter_normalized_dev = c.out[2];
     const int f = cfg->fft_size;
     // stage 1 (stages.py:38-104): both tracks analysed in one pass each -- or the target alone, against a profile
-    TrackWork& tw = h->track[0];
-    TrackWork& rw = h->track[1];
+    CallContext& cx = h->ctx[plan.context];
+    TrackWork& tw = cx.track[0];
+    TrackWork& rw = cx.track[1];
     const mgx_profile_header* profile = c.profile;
+    // the front half's stream for the length of this call; whatever way out, the stage-level entry points find main
+    struct FrontQueue {
+        mgx_handle* h;
+        ~FrontQueue() { h->fq = h->stream; }
+    } front_queue{h};
+    if (plan.pipelined) {
+        h->fq = h->front;
+        if (plan.wait_context) HIP_TRY(hipStreamWaitEvent(h->front, h->back_done[plan.context], 0));        // (a)
+        if (plan.wait_main) {                                                                                // (b)
+            HIP_TRY(hipEventRecord(h->main_now, h->stream));
+            HIP_TRY(hipStreamWaitEvent(h->front, h->main_now, 0));
+        }
+    }
     // where stages 3 and 4 read the reference's two scalars: its TrackStats, or the profile's header
     const double* reference_match_rms = profile ? &profile->match_rms : nullptr;
     const double* reference_amplitude_c = profile ? &profile->amplitude_coefficient : nullptr;
@@ -2058,10 +2158,17 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
     MGX_TRY(ensure(h, h->y, (size_t)n_target * sizeof(float2)));
     MGX_TRY(ensure(h, h->mid, (size_t)n_target * sizeof(float)));
     long long nblocks = 0;
-    MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)h->taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
-                     &nblocks, (const double*)h->scalars.p));
+    MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)cx.taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
+                     &nblocks, (const double*)cx.scalars.p, CONV_SPECTRA));
+    if (plan.pipelined) {       // (c) the front half ends here, (d) the back half follows it on main
+        HIP_TRY(hipEventRecord(h->front_done[plan.context], h->front));
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->front_done[plan.context], 0));
+        h->fq = h->stream;
+    }
+    MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)cx.taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
+                     &nblocks, (const double*)cx.scalars.p, CONV_MAIN));
     // stage 3 (stages.py:138-170): scalar feedback stays on the device (the state was reset by k_fir_raw)
-    CorrectionState* cs = (CorrectionState*)h->cstate.p;
+    CorrectionState* cs = (CorrectionState*)cx.cstate.p;
     bool limiter_preset = false;
     {
         StageScope scope(h, MGX_STAGE_CORRECT_LEVELS);
@@ -2083,6 +2190,7 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c) {
                             &cs->limiter_active,
                             result_dev, limiter_preset));
     }
+    if (plan.record_back && h->front) HIP_TRY(hipEventRecord(h->back_done[plan.context], h->stream));
     return 0;
 }
 
@@ -2112,12 +2220,40 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
     call.out[0] = result_dev;
     call.out[1] = result_no_limiter_dev;
     call.out[2] = result_no_limiter_normalized_dev;
-    MGX_TRY(queue_master(h, call));
+    MasterRanges ranges;
+    const size_t fir_bytes = (size_t)2 * cfg->fft_size * sizeof(float);
+    size_t profile_bytes = 0;
+    if (profile) MGX_TRY(mgx_profile_bytes(cfg, &profile_bytes));
+    ranges.in[0] = byte_range(target_dev, (size_t)n_target * sizeof(float2));
+    ranges.in[1] = byte_range(reference_dev, (size_t)n_reference * sizeof(float2));
+    ranges.in[2] = byte_range(profile, profile_bytes);
+    ranges.in[3] = byte_range(fir_given, fir_bytes);
+    for (int i = 0; i < 3; ++i) ranges.out[i] = byte_range(call.out[i], (size_t)n_target * sizeof(float2));
+    for (const CallContext& other : h->ctx)
+        if (overlap(ranges.in[3], byte_range(other.taps.p, other.taps.bytes))) ranges.reads_context_taps = true;
+    // on main alone: stage events bracket one stream's work, and a report waits for the call's scalars before it returns.
+    // So does every handle of a device that has several: the lanes of a batch fill each other's idle stretches already,
+    // and with front streams beside them they were measured a fifth slower
+    bool alone;
+    {
+        LimiterChain& chain = g_limiter_chain[h->device % MAX_DEVICES];
+        std::lock_guard<std::mutex> lock(chain.mu);
+        alone = chain.live == 1;
+    }
+    if (alone) MGX_TRY(ensure_front(h));
+    const MasterPlan plan = h->pipe.master(ranges, h->stage_timing || report != nullptr || !alone || !h->front);
+    const int rc = queue_master(h, call, plan);
+    if (rc != 0) {              // a front half may be left without its back half: nothing stays in flight
+        drain(h);
+        h->pipe.drained();
+        return rc;
+    }
     call.valid = true;
     ++h->masters_outstanding;
-    TrackWork& tw = h->track[0];
-    TrackWork& rw = h->track[1];
-    CorrectionState* cs = (CorrectionState*)h->cstate.p;
+    CallContext& cx = h->ctx[plan.context];
+    TrackWork& tw = cx.track[0];
+    TrackWork& rw = cx.track[1];
+    CorrectionState* cs = (CorrectionState*)cx.cstate.p;
     if (report) {
         MGX_TRY(ensure_pinned(h, 1 << 16));
         char* pin = (char*)h->pinned;
@@ -2133,8 +2269,8 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
             else
                 HIP_TRY(hipMemcpyAsync(st_r, rw.stats.p, sizeof(TrackStats), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipMemcpyAsync(hc, cs, sizeof(CorrectionState), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipMemcpyAsync(c0, h->scalars.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
+            HIP_TRY(hipMemcpyAsync(c0, cx.scalars.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            MGX_TRY(sync_main(h));
             MGX_TRY(check_device_error(h, true));                 // (nothing of the run has been handed out yet)
             if (!h->requeued) break;
         }
@@ -2196,7 +2332,8 @@ int mgx_reference_profile(mgx_handle* h, const float* reference_dev, int64_t n_r
     MGX_TRY(check_config(cfg));
     HIP_TRY(hipSetDevice(h->device));
     // mgx_analyze(is_reference = 1)'s chain, then the pack
-    TrackWork& w = h->track[1];
+    h->pipe.other_work();
+    TrackWork& w = context(h).track[1];
     w.is_reference = 1;
     MGX_TRY(run_analysis(h, cfg, reference_dev, n_reference, w));
     MGX_TRY(run_levels(h, cfg, &w, nullptr));
@@ -2243,6 +2380,7 @@ int mgx_profile_merge(mgx_handle* h, const void* const* profiles_dev, const int3
         a.weight[i] = w;
     }
     HIP_TRY(hipSetDevice(h->device));
+    h->pipe.other_work();
     const int bins = cfg->fft_size / 2 + 1;
     hipLaunchKernelGGL(k_profile_merge, dim3((2 * bins + 255) / 256), dim3(256), 0, h->stream, a, profile_want(cfg), bins,
                        (mgx_profile_header*)profile_dev, h->error_dev);
@@ -2271,7 +2409,7 @@ int mgx_dev_phase_ticks_read(unsigned* out, int chunks) {       // out: [chunks]
 #endif
 int mgx_stage_times(mgx_handle* h, float* ms) {
     if (!h || !ms) return fail(MGX_ERR_ARGUMENT, "null argument");
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    MGX_TRY(sync_main(h));
     for (int s = 0; s < MGX_STAGE_COUNT; ++s) {
         ms[s] = -1.f;
         if (!h->stage_used[s]) continue;
@@ -2292,9 +2430,10 @@ int mgx_code_bytes(int32_t* bytes, int32_t capacity) {
 
 int mgx_last_fir(mgx_handle* h, void** taps_dev, int32_t* taps) {
     if (!h || !taps_dev || !taps) return fail(MGX_ERR_ARGUMENT, "null argument");
-    if (!h->taps.p || h->last_taps <= 0) return fail(MGX_ERR_ARGUMENT, "no FIR has been designed on this handle yet");
-    *taps_dev = h->taps.p;
-    *taps = h->last_taps;
+    CallContext& cx = context(h);
+    if (!cx.taps.p || cx.last_taps <= 0) return fail(MGX_ERR_ARGUMENT, "no FIR has been designed on this handle yet");
+    *taps_dev = cx.taps.p;
+    *taps = cx.last_taps;
     return 0;
 }
 
@@ -2332,11 +2471,13 @@ int mgx_comm_count(mgx_handle* h, int32_t* ranks) {
 }
 int mgx_comm_broadcast_f32(mgx_handle* h, float* dev, int64_t count, int root) {
     if (!h || !h->comm) return fail(MGX_ERR_ARGUMENT, "communicator not initialised");
+    h->pipe.other_work();
     NCCL_TRY(ncclBroadcast(dev, dev, (size_t)count, ncclFloat, root, h->comm, h->stream));
     return 0;
 }
 int mgx_comm_allgather_f32(mgx_handle* h, const float* send_dev, float* recv_dev, int64_t count) {
     if (!h || !h->comm) return fail(MGX_ERR_ARGUMENT, "communicator not initialised");
+    h->pipe.other_work();
     NCCL_TRY(ncclAllGather(send_dev, recv_dev, (size_t)count, ncclFloat, h->comm, h->stream));
     return 0;
 }
