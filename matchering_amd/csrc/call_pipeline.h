@@ -7,6 +7,11 @@
 // outputs).  Back halves stay on the handle's main stream, one behind the other.  The front half of call k may run on
 // a second stream, under the back half of call k - 1, because it depends on nothing that call computes -- unless the
 // handle is "dirty" for this call, in which case it first waits for everything queued on main so far.
+//
+// The back half itself lets go of the context early: behind round 0 of its level correction nothing of the call touches
+// the context any more (mgx.hip, CallContext and BackState).  The event of wait (a) is recorded there, so the front half
+// of call k may also run beside the tail, the scale kernel and the limiter of call k - 2.  The planner does not care
+// where in the back half the event lies: `record_back` says that it is recorded, `wait_context` that it is waited for.
 #pragma once
 #include <cstdint>
 
@@ -36,9 +41,9 @@ struct MasterRanges {
 struct MasterPlan {
     int context = 0;            // the CallContext of this call: the other one for a pipelined call, the current one else
     bool pipelined = false;     // front half on the front stream, (c) and (d); else the whole call on main as ever
-    bool wait_context = false;  // (a) front waits for back_done[context]: call k - 2 has let go of the context
+    bool wait_context = false;  // (a) front waits for ctx_released[context]: call k - 2 has let go of the context
     bool wait_main = false;     // (b) front waits for an event recorded on main now: the call is dirty
-    bool record_back = false;   // back_done[context] is recorded behind the back half
+    bool record_back = false;   // ctx_released[context] is recorded in the back half, behind its last launch that touches the context
 };
 
 class CallPipeline {
@@ -57,8 +62,12 @@ public:
 private:
     int current_ = 0;
     bool dirty_ = false;                            // other_work() since the previous master call
-    bool busy_[CALL_CONTEXTS] = {};                 // back_done[c] recorded and not known to have passed
-    ByteRange recent_out_[2][3];                    // the outputs of the previous two master calls
+    bool busy_[CALL_CONTEXTS] = {};                 // ctx_released[c] recorded and not known to have passed
+    // The outputs of the previous two master calls.  Two are enough although the front half of call k + 2 may run while
+    // the limiter of call k still writes its result: when call k + 2 is planned these are the outputs of calls k + 1 and
+    // k, exactly the back halves that may still be running.  Every older one has finished before that front half starts:
+    // it waits for call k's round 0 (wait (a)), which lies on main behind the whole back half of call k - 1.
+    ByteRange recent_out_[2][3];
 };
 
 }  // namespace mgx

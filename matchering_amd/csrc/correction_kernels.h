@@ -39,6 +39,18 @@ struct CorrectionState {
     int limiter_active;
     int steps_done;
 };
+// What a call's back half reads and writes once round 0 of the level correction has been launched: the correction
+// state and the reference's two scalars.  One per handle (mgx.hip, mgx_handle::back), like y and mid, not one per
+// call context: round 0's launch (k_finalize_scalars where there are no rounds) copies the state the front half reset
+// and the two scalars out of the context, and every launch behind it works here.  The context is then free for the
+// front half of the next call but one.
+struct BackState {
+    CorrectionState cs;
+    double reference_match_rms;         // TrackStats::match_rms of the reference, or its profile's
+    double reference_amplitude_c;       // ... and its amplitude coefficient (the limiter's post gain)
+};
+static_assert(offsetof(BackState, reference_amplitude_c) == offsetof(BackState, reference_match_rms) + sizeof(double),
+              "RoundArgs::back_refs addresses the two scalars as [0] and [1]");
 
 // partial[d*chunks + ch] = sum over the chunk of clip(gain*mid, -1, 1)^2
 __global__ __launch_bounds__(256) void k_clipped_sumsq(const float* mid, long long piece, int chunks,
@@ -127,9 +139,14 @@ struct RoundArgs {
     int chunks, divisions;
     double* partial;            // [divisions][chunks]
     unsigned* arrivals;         // [1 + divisions] counters, zero between launches: [0] pieces done, [1+d] chunks of piece d
-    const double* reference_match_rms;
+    const double* reference_match_rms;      // round 0: in the reference's TrackStats or profile; later launches: in the BackState
     double eps, threshold;
-    CorrectionState* cs;
+    CorrectionState* cs;                    // the BackState's
+    // round 0 alone (null in every later launch): what it copies into the BackState (back_state_fill) -- the context's
+    // state as the front half reset it (-> *cs), *reference_match_rms and *front_amplitude_c (-> back_refs[0], [1])
+    const CorrectionState* front_cs;
+    const double* front_amplitude_c;
+    double* back_refs;
     const float* final_peaks;   // per-pair peaks of the convolution, or null
     long long npeaks;
     float* band;                // [n + workgroups * BAND_SLACK] compacted band samples
@@ -149,6 +166,38 @@ struct RoundArgs {
                                       // with one, this launch leaves its partials and the decision to that kernel
     int tail_rounds;                  // rounds that kernel runs (rms_correction_steps - 1; any number: defaults.py:118-120)
     int* error;                       // set when a bounded wait expired
+};
+// Round 0's copy into the BackState.  Where the launch takes a decision, the ONE thread that takes it copies first (its
+// stores to *cs follow the copy in program order).  Where k_correction_tail decides, the copy rides along in workgroup
+// 0 (BackFillLane): nobody else writes the BackState in that launch.  The launch boundary makes it visible to whatever
+// follows.
+__device__ __forceinline__ void back_state_fill(const RoundArgs& a) {
+    if (!a.front_cs) return;
+    *a.cs = *a.front_cs;
+    a.back_refs[0] = *a.reference_match_rms;
+    a.back_refs[1] = *a.front_amplitude_c;
+}
+// The same copy as one 8-byte word per lane: loaded on entry, stored on exit, so that the latency of the (cold) loads
+// passes under the workgroup's own streaming instead of holding its first wave up before it starts (a thread that
+// loaded and stored on the spot made workgroup 0, and with it the launch, about a microsecond late).
+typedef unsigned long long __attribute__((may_alias)) back_word;
+constexpr int BACK_STATE_WORDS = (int)(sizeof(CorrectionState) / sizeof(back_word));
+static_assert(sizeof(CorrectionState) % sizeof(back_word) == 0, "the CorrectionState is copied in 8-byte words");
+struct BackFillLane {
+    back_word word = 0;
+    back_word* to = nullptr;
+    __device__ __forceinline__ void load(const RoundArgs& a, int w) {
+        if (!a.front_cs || w >= BACK_STATE_WORDS + 2) return;
+        const back_word* from = w < BACK_STATE_WORDS    ? reinterpret_cast<const back_word*>(a.front_cs) + w
+                                : w == BACK_STATE_WORDS ? reinterpret_cast<const back_word*>(a.reference_match_rms)
+                                                        : reinterpret_cast<const back_word*>(a.front_amplitude_c);
+        to = w < BACK_STATE_WORDS ? reinterpret_cast<back_word*>(a.cs) + w
+                                  : reinterpret_cast<back_word*>(a.back_refs) + (w - BACK_STATE_WORDS);
+        word = *from;
+    }
+    __device__ __forceinline__ void store() const {
+        if (to) *to = word;
+    }
 };
 // The decision of one round (stages.py:149-168), taken by ONE 256-thread workgroup after every partial
 // sum has been published: piece sums -> loud pieces -> coefficient -> accumulated gain; with
@@ -191,6 +240,7 @@ __device__ __forceinline__ double correction_decide(const RoundArgs& a, int tota
     if (threadIdx.x < 64) wave_decide(sums, a.divisions, a.piece, 1.0, nullptr, nullptr, avg, match, count);
     if (threadIdx.x == 0) {
         const double c = *a.reference_match_rms / fmax(a.eps, match);      // match_levels.py:106-111
+        back_state_fill(a);
         CorrectionState* cs = a.cs;
         new_gain = gain_in * c;
         if (step < 16) cs->coeffs[step] = c;
@@ -220,10 +270,12 @@ __global__ __launch_bounds__(256) void k_correction_round(RoundArgs a) {
     const int d = blockIdx.x / a.chunks, ch = blockIdx.x % a.chunks;
     const BandChunk bc = band_chunk(a.band, a.piece, a.chunks, d, ch);
     const long long b = bc.b, e = bc.e;
-    const double g = a.cs->gain;
+    const double g = (a.front_cs ? a.front_cs : a.cs)->gain;    // (round 0 starts from the context's state: the copy is under way)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (a.tail_gains && blockIdx.x == 0)                                                         // "not yet": k_correction_tail
         for (int i = threadIdx.x; i < a.tail_rounds + 1 + a.tail_rounds * a.tail_total; i += 256) a.tail_gains[i] = ~0ull;
+    BackFillLane back_fill;                                     // (no decision in this launch: stored on the way out)
+    if (a.build_band && a.tail_total > 0 && blockIdx.x == 0) back_fill.load(a, threadIdx.x);
     if (a.lim_published) {
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.lim_words; i += (long long)gridDim.x * 256)
             a.lim_published[i] = ~0ull;
@@ -361,6 +413,7 @@ __global__ __launch_bounds__(256) void k_correction_round(RoundArgs a) {
     const double s = block_sum<256>(acc, red);
     if (a.build_band && a.tail_total > 0) {                              // uniform: k_correction_tail decides round 0
         if (threadIdx.x == 0) a.partial[blockIdx.x] = s;
+        back_fill.store();
         return;
     }
     if (threadIdx.x == 0) {
@@ -675,13 +728,22 @@ __global__ void k_correction_init(CorrectionState* cs, double gain) {
 
 // peak of the corrected result, limiter early-out decision (hyrax.py:83-85 with numpy.isclose
 // defaults) and the normalisation coefficient of stages.py:186-191 / dsp.py:93-100
+// `front_cs`: a master call without correction rounds, whose BackState this launch fills as round 0 would
+// (back_state_fill): *front_cs -> *cs, the reference's two scalars -> back_refs[0], [1].  Null: *cs is the caller's.
 __global__ __launch_bounds__(256) void k_finalize_scalars(const float* block_peak, long long nblocks,
-                                                          double threshold, double eps, CorrectionState* cs) {
+                                                          double threshold, double eps, CorrectionState* cs,
+                                                          const CorrectionState* front_cs, const double* front_match_rms,
+                                                          const double* front_amplitude_c, double* back_refs) {
     __shared__ float scratch[4];
     float m = 0.f;
     for (long long i = threadIdx.x; i < nblocks; i += 256) m = fmaxf(m, block_peak[i]);
     const float pk = block_max<256>(m, scratch);
     if (threadIdx.x == 0) {
+        if (front_cs) {
+            *cs = *front_cs;
+            back_refs[0] = *front_match_rms;
+            back_refs[1] = *front_amplitude_c;
+        }
         const double peak = (double)(float)((double)pk * cs->gain);      // max |float32(y*gain)|
         cs->result_peak = peak;
         const double rect = fmax(peak, threshold) / threshold;

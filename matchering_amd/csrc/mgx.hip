@@ -126,6 +126,12 @@ static LimiterChain g_limiter_chain[MAX_DEVICES];
 // What the front half of a master call (analysis, FIR design, filter spectra) writes and its back half reads.  A
 // handle owns CALL_CONTEXTS of them, so that the next call's front half can run under this call's back half
 // (call_pipeline.h); everything only back halves touch stays single in the handle.
+// THE INVARIANT THE PIPELINE RESTS ON: once the launch of round 0 of a call's level correction has finished
+// (k_correction_round with build_band; k_finalize_scalars for a call without rounds), nothing of that call reads or
+// writes its CallContext.  That launch moves the last things the rest of the back half needs -- the correction state
+// the front half reset and the reference's two scalars -- into the handle's BackState (mgx_handle::back); the tail,
+// the later rounds, the scale kernel, the limiter and the report work there.  So the context is handed to the front
+// half of the next call but one right behind that launch (ctx_released), not behind the limiter.
 struct CallContext {
     TrackWork track[2];
     DevBuf fir_scratch, scalars, taps, filt, cstate;
@@ -141,7 +147,11 @@ struct mgx_handle {
     hipStream_t fq = nullptr;               // where the front-half runners queue: `stream`, or `front` inside a pipelined call
     CallPipeline pipe;
     CallContext ctx[CALL_CONTEXTS];         // a pipelined call takes the other one; the stage-level entry points use the most recent call's
-    hipEvent_t front_done[CALL_CONTEXTS] = {}, back_done[CALL_CONTEXTS] = {};
+    // front_done[c]: behind the front half that filled context c.  ctx_released[c]: behind the last launch of the call
+    // in context c that touches the context (round 0 of its level correction) -- what wait (a) of the next user's front
+    // half needs, and NOT the end of that call's back half: whoever needs the whole back half (ensure / ensure_pinned
+    // before freeing, mgx_free, mgx_destroy, drain, the planner's drained()) synchronises main itself.
+    hipEvent_t front_done[CALL_CONTEXTS] = {}, ctx_released[CALL_CONTEXTS] = {};
     hipEvent_t main_now = nullptr;          // wait (b): recorded on main when a dirty call's front half starts
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool stage_timing = false;                                    // mgx_stage_timing
@@ -149,6 +159,7 @@ struct mgx_handle {
     bool stage_used[MGX_STAGE_COUNT] = {};
     std::map<int, float2*> twiddles;
     DevBuf y, mid, block_peak, partial, conv_queue;
+    DevBuf back;                            // one BackState: filled by round 0 of each call, the rest of its back half works here
     DevBuf lim_published, lim_ctrl, lim_weights, round_ctr, tail_gains, band, band_info;
     std::vector<double> lim_weights_host;
     DevBuf peak_words;                      // mgx_peak_count: {bits of the maximum, count}
@@ -232,10 +243,10 @@ static int ensure_front(mgx_handle* h) {
     if (h->front) return 0;
     int least = 0, greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    for (hipEvent_t* e : {&h->front_done[0], &h->front_done[1], &h->back_done[0], &h->back_done[1], &h->main_now})
+    for (hipEvent_t* e : {&h->front_done[0], &h->front_done[1], &h->ctx_released[0], &h->ctx_released[1], &h->main_now})
         HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithPriority(&h->front, hipStreamNonBlocking, least));
-    // (no back_done was recorded behind the calls so far: the first front half waits for everything main holds instead)
+    // (no ctx_released was recorded behind the calls so far: the first front half waits for everything main holds instead)
     h->pipe.other_work();
     return 0;
 }
@@ -1001,11 +1012,18 @@ static const char* const TOO_MANY_PIECES = "too many analysis pieces for the lev
 // Stage 3 (stages.py:138-170), every round queued on the handle's stream: one launch per round, the last round also
 // derives the peak / early-out / normalisation scalars.  `nblocks`: the per-pair peaks the convolution left in
 // h->block_peak.  `lp`: the limiter's parameters when a limited result follows, else null; round 0's grid then presets
-// the limiter's look-back words (`*limiter_preset`).  `reference_match_rms`: device address of the reference's match RMS
-// (the reference's TrackStats, or a profile's header).
-static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const double* reference_match_rms,
-                          long long n_target, long long nblocks, const LimiterParams* lp, bool* limiter_preset) {
-    CorrectionState* cs = (CorrectionState*)context(h).cstate.p;
+// the limiter's look-back words (`*limiter_preset`).  `reference_match_rms`, `reference_amplitude_c`: device addresses
+// of the reference's two scalars (the reference's TrackStats, or a profile's header).
+// The first launch here (round 0, or k_finalize_scalars where there are no rounds) is the last of the call that touches
+// its context `cx`: it starts from cx.cstate, as the front half reset it, and fills the handle's BackState, where every
+// later launch of the back half reads and writes.  `released` (or null) is recorded right behind it.
+static int run_correction(mgx_handle* h, const mgx_config* cfg, const CallContext& cx, const double* reference_match_rms,
+                          const double* reference_amplitude_c, long long n_target, long long nblocks,
+                          const LimiterParams* lp, bool* limiter_preset, hipEvent_t released) {
+    const TrackWork& tw = cx.track[0];
+    MGX_TRY(ensure(h, h->back, sizeof(BackState)));
+    BackState* back = (BackState*)h->back.p;
+    CorrectionState* cs = &back->cs;
     RoundArgs ra;
     ra.mid = (const float*)h->mid.p;
     ra.piece = tw.piece;
@@ -1036,7 +1054,10 @@ static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork&
     MGX_TRY(ensure(h, h->band_info, wgs * sizeof(BandInfo)));
     ra.band = (float*)h->band.p;
     ra.info = (BandInfo*)h->band_info.p;
-    ra.reference_match_rms = reference_match_rms;
+    ra.reference_match_rms = &back->reference_match_rms;
+    ra.front_cs = nullptr;
+    ra.front_amplitude_c = nullptr;
+    ra.back_refs = nullptr;
     ra.eps = cfg->min_value;
     ra.threshold = cfg->threshold;
     ra.cs = cs;
@@ -1056,11 +1077,16 @@ static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork&
         r0.final_peaks = rounds == 1 ? (const float*)h->block_peak.p : nullptr;    // (the launch of the last round)
         r0.build_band = 1;
         r0.step = 0;
+        r0.reference_match_rms = reference_match_rms;
+        r0.front_cs = (const CorrectionState*)cx.cstate.p;
+        r0.front_amplitude_c = reference_amplitude_c;
+        r0.back_refs = &back->reference_match_rms;
         if (lp) {     // the limiter's look-back words are preset by this grid: a thousand workgroups, two words a thread
             MGX_TRY(limiter_state(h, n_target, *lp, &r0.lim_published, &r0.lim_words, &r0.lim_ticket));
             *limiter_preset = true;
         }
         hipLaunchKernelGGL(k_correction_round, dim3(ra.divisions * ra.chunks), dim3(256), lds_step, h->stream, r0);
+        if (released) HIP_TRY(hipEventRecord(released, h->stream));
     }
     if (rounds > 1 && !use_tail) {
         // one launch per round, the last arriver of each decides (k_correction_round without a tail): what a handle
@@ -1086,9 +1112,12 @@ static int run_correction(mgx_handle* h, const mgx_config* cfg, const TrackWork&
         hipLaunchKernelGGL(k_correction_tail, dim3(ra.divisions * groups + 1), dim3(256), lds_tail, h->stream, rt, groups,
                            rounds - 1);
     }
-    if (rounds == 0)
+    if (rounds == 0) {
         hipLaunchKernelGGL(k_finalize_scalars, dim3(1), dim3(256), 0, h->stream, (const float*)h->block_peak.p,
-                           nblocks, cfg->threshold, cfg->min_value, cs);
+                           nblocks, cfg->threshold, cfg->min_value, cs, (const CorrectionState*)cx.cstate.p,
+                           reference_match_rms, reference_amplitude_c, &back->reference_match_rms);
+        if (released) HIP_TRY(hipEventRecord(released, h->stream));
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1442,7 +1471,7 @@ int mgx_destroy(mgx_handle* h) {
     for (auto& pair : h->stage_ev)
         for (hipEvent_t e : pair)
             if (e) hipEventDestroy(e);
-    for (hipEvent_t e : {h->front_done[0], h->front_done[1], h->back_done[0], h->back_done[1], h->main_now})
+    for (hipEvent_t e : {h->front_done[0], h->front_done[1], h->ctx_released[0], h->ctx_released[1], h->main_now})
         if (e) hipEventDestroy(e);
     if (h->front) hipStreamDestroy(h->front);
     hipStreamDestroy(h->stream);
@@ -1635,12 +1664,12 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
     MGX_TRY(check_config(cfg));
     HIP_TRY(hipSetDevice(h->device));
     h->pipe.other_work();
-    CallContext& cx = context(h);
-    // peak -> early-out decision, through the same kernels the pipeline uses
-    MGX_TRY(ensure(h, cx.cstate, sizeof(CorrectionState)));
-    MGX_TRY(ensure(h, cx.scalars, 64));
+    // peak -> early-out decision, through the same kernels the pipeline uses, in the handle's BackState as a master
+    // call's limiter finds them (on main, behind every back half queued so far; no call context is touched)
+    MGX_TRY(ensure(h, h->back, sizeof(BackState)));
     MGX_TRY(ensure_pinned(h, 1 << 16));
-    CorrectionState* cs = (CorrectionState*)cx.cstate.p;
+    BackState* back = (BackState*)h->back.p;
+    CorrectionState* cs = &back->cs;
     hipLaunchKernelGGL(k_correction_init, dim3(1), dim3(1), 0, h->stream, cs, gain);
     // per-block peaks of x via the scale kernel's sibling: reuse k_finalize on a peak pass
     const long long nb = (n + 4095) / 4096;
@@ -1648,10 +1677,11 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
     hipLaunchKernelGGL(k_frame_peaks, dim3((unsigned)nb), dim3(256), 0, h->stream, (const float2*)x_dev, (long long)n,
                        (float*)h->block_peak.p);
     hipLaunchKernelGGL(k_finalize_scalars, dim3(1), dim3(256), 0, h->stream, (const float*)h->block_peak.p, nb,
-                       cfg->threshold, cfg->min_value, cs);
+                       cfg->threshold, cfg->min_value, cs, (const CorrectionState*)nullptr, (const double*)nullptr,
+                       (const double*)nullptr, (double*)nullptr);
     double* post = (double*)h->pinned;
     *post = post_gain;
-    HIP_TRY(hipMemcpyAsync(cx.scalars.p, post, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(&back->reference_amplitude_c, post, sizeof(double), hipMemcpyHostToDevice, h->stream));
     CorrectionState host_cs;
     // Error words that earlier asynchronous mgx_master calls may have left are THEIRS: looked at (and reported) before
     // this call queues anything, so that the retry below can only ever answer for this call's own limiter.
@@ -1664,7 +1694,7 @@ int mgx_limit(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* cf
     if (!err.empty()) return fail(MGX_ERR_UNSUPPORTED, err);
     for (int attempt = 0;; ++attempt) {
         const bool tickets_before = h->limiter_tickets;
-        MGX_TRY(run_limiter(h, x_dev, n, lp, cfg->threshold, &cs->gain, (const double*)cx.scalars.p, &cs->limiter_active,
+        MGX_TRY(run_limiter(h, x_dev, n, lp, cfg->threshold, &cs->gain, &back->reference_amplitude_c, &cs->limiter_active,
                             out_dev));
         HIP_TRY(hipMemcpyAsync(&host_cs, cs, sizeof(host_cs), hipMemcpyDeviceToHost, h->stream));
         MGX_TRY(sync_main(h));
@@ -2126,7 +2156,9 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const Ma
     } front_queue{h};
     if (plan.pipelined) {
         h->fq = h->front;
-        if (plan.wait_context) HIP_TRY(hipStreamWaitEvent(h->front, h->back_done[plan.context], 0));        // (a)
+        // (a) the context's previous user, call k - 2, has let go of it: round 0 of its level correction has finished.
+        // Its tail, scale kernel and limiter may still be running or waiting: they touch the BackState only.
+        if (plan.wait_context) HIP_TRY(hipStreamWaitEvent(h->front, h->ctx_released[plan.context], 0));
         if (plan.wait_main) {                                                                                // (b)
             HIP_TRY(hipEventRecord(h->main_now, h->stream));
             HIP_TRY(hipStreamWaitEvent(h->front, h->main_now, 0));
@@ -2167,14 +2199,18 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const Ma
     }
     MGX_TRY(run_conv(h, target_dev, n_target, f, (const float*)cx.taps.p, 1.0, (float*)h->y.p, (float*)h->mid.p,
                      &nblocks, (const double*)cx.scalars.p, CONV_MAIN));
-    // stage 3 (stages.py:138-170): scalar feedback stays on the device (the state was reset by k_fir_raw)
-    CorrectionState* cs = (CorrectionState*)cx.cstate.p;
+    // stage 3 (stages.py:138-170): scalar feedback stays on the device (the state was reset by k_fir_raw).  Its first
+    // launch is the last that touches `cx`; the context is released behind it, and from here on the call works in the
+    // handle's BackState.
     bool limiter_preset = false;
     {
         StageScope scope(h, MGX_STAGE_CORRECT_LEVELS);
-        MGX_TRY(run_correction(h, cfg, tw, reference_match_rms, n_target, nblocks, result_dev ? &c.lp : nullptr,
-                               &limiter_preset));
+        MGX_TRY(run_correction(h, cfg, cx, reference_match_rms, reference_amplitude_c, n_target, nblocks,
+                               result_dev ? &c.lp : nullptr, &limiter_preset,
+                               plan.record_back && h->front ? h->ctx_released[plan.context] : nullptr));
     }
+    const BackState* back = (const BackState*)h->back.p;
+    const CorrectionState* cs = &back->cs;
     // stage 4 (stages.py:173-207)
     if (result_no_limiter_dev || result_no_limiter_normalized_dev) {
         StageScope scope(h, MGX_STAGE_SCALE_OUTPUTS);
@@ -2186,11 +2222,9 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const Ma
     }
     if (result_dev) {
         StageScope scope(h, MGX_STAGE_LIMIT);
-        MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, c.lp, cfg->threshold, &cs->gain, reference_amplitude_c,
-                            &cs->limiter_active,
-                            result_dev, limiter_preset));
+        MGX_TRY(run_limiter(h, (const float*)h->y.p, n_target, c.lp, cfg->threshold, &cs->gain,
+                            &back->reference_amplitude_c, &cs->limiter_active, result_dev, limiter_preset));
     }
-    if (plan.record_back && h->front) HIP_TRY(hipEventRecord(h->back_done[plan.context], h->stream));
     return 0;
 }
 
@@ -2253,7 +2287,9 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
     CallContext& cx = h->ctx[plan.context];
     TrackWork& tw = cx.track[0];
     TrackWork& rw = cx.track[1];
-    CorrectionState* cs = (CorrectionState*)cx.cstate.p;
+    const CorrectionState* cs = &((const BackState*)h->back.p)->cs;      // (where the call's rounds left their results)
+    // (a call with a report ran on main alone and waits below before anything else is queued: its copies may still read
+    // the analysis results and the level gain in the context)
     if (report) {
         MGX_TRY(ensure_pinned(h, 1 << 16));
         char* pin = (char*)h->pinned;

@@ -1,7 +1,10 @@
 """Do consecutive master steps overlap?  From a rocprofv3 results .db (kernel-trace) of back-to-back steps: per step
 (one k_analyze launch to the next), the microseconds in which no kernel runs, in which only the small kernels run (the
 FIR-design chain, the filter spectra, the level-correction tail) and in which a big kernel runs; and which kernels of
-step k the analysis of step k + 1 runs under.
+step k the analysis of step k + 1 runs under.  Then, per launch of k_correction_tail -- the one stretch of a
+step's back half that leaves most of the chip idle -- which kernels run while it runs and for how long, and how long after
+its end the step's k_limit starts (the context is released behind round 0, so the analysis of the step after next
+belongs there).
 
     python tools/pipeline_timeline.py results.db
 """
@@ -44,6 +47,20 @@ def main():
                  for i, (n, s, e) in enumerate(rows) if i != firsts[k + 1] and s < ae and e > as_]
         ahead = "%.1f us before this step's k_limit ends; " % ((limits[k][2] - as_) / 1e3) if k < len(limits) else ""
         print("%4d %9.1f %9.1f %9.1f %9.1f   %s%s" % (k, (t1 - t0) / 1e3, idle, small, big, ahead, ", ".join(under) or "nothing"))
+    tails = [r for r in rows if "k_correction_tail" in r[0]]
+    print()
+    print("%4s %9s %9s %9s %9s   %s" % ("tail", "runs", "conv", "round 0", "-> limit", "beside the tail"))
+    for k, (_, ts, te) in enumerate(tails):
+        beside = ["%s %.1f us%s" % (short(n), (min(e, te) - max(s, ts)) / 1e3,
+                                   " (starts %+.1f us from the tail's start)" % ((s - ts) / 1e3) if "k_analyze" in n else "")
+                  for n, s, e in rows if (s, e) != (ts, te) and s < te and e > ts]
+        # the convolution and round 0 of the same step: the last of each that started before this tail
+        conv = [(e - s) / 1e3 for n, s, e in rows if "k_conv" in n and "prep" not in n and s < ts]
+        round0 = [(e - s) / 1e3 for n, s, e in rows if "k_correction_round" in n and s < ts]
+        limit = [(s - te) / 1e3 for n, s, e in rows if "k_limit" in n and s >= ts]
+        print("%4d %9.1f %9s %9s %9s   %s" % (k, (te - ts) / 1e3, "%.1f" % conv[-1] if conv else "-",
+                                             "%.1f" % round0[-1] if round0 else "-", "%+.1f" % limit[0] if limit else "-",
+                                             ", ".join(beside) or "nothing"))
 
 
 if __name__ == "__main__":
