@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libmgx.so")
 SOURCES = [os.path.join(CSRC, "mgx.hip"), os.path.join(CSRC, "fir_design.cpp"), os.path.join(CSRC, "fir_plan.cpp"),
            os.path.join(CSRC, "resample_plan.cpp"), os.path.join(CSRC, "loudness_plan.cpp"),
-           os.path.join(CSRC, "call_pipeline.cpp")]
+           os.path.join(CSRC, "call_pipeline.cpp"), os.path.join(CSRC, "mgx_policy.cpp")]
 
 
 def _deps():

@@ -1,5 +1,5 @@
 // Which per-call context an mgx_master call uses and which event waits order it against its neighbours.
-// Pure host code, no HIP: mgx.hip only executes what master() returns, and tests/test_call_pipeline_host.py drives
+// Pure host code, no HIP: master_call.h only executes what master() returns, and tests/test_call_pipeline_host.py drives
 // this unit with generated call sequences on a machine without a GPU.
 //
 // A master call has a FRONT half (analysis, FIR design, filter spectra: reads the call's inputs, writes its context)
@@ -9,7 +9,7 @@
 // handle is "dirty" for this call, in which case it first waits for everything queued on main so far.
 //
 // The back half itself lets go of the context early: behind round 0 of its level correction nothing of the call touches
-// the context any more (mgx.hip, CallContext and BackState).  The event of wait (a) is recorded there, so the front half
+// the context any more (handle.h, CallContext; correction_kernels.h, BackState).  The event of wait (a) is recorded there, so the front half
 // of call k may also run beside the tail, the scale kernel and the limiter of call k - 2.  The planner does not care
 // where in the back half the event lies: `record_back` says that it is recorded, `wait_context` that it is waited for.
 #pragma once

@@ -1,4 +1,4 @@
-// The level-correction stage (stages.py:138-170) on the device; the host side is run_correction in mgx.hip.
+// The level-correction stage (stages.py:138-170) on the device; the host side is run_correction.h.
 // Device only, and the only place this logic exists:
 //   * CorrectionState, the stage's scalars, and k_clipped_sumsq (the stage-level API's one round),
 //   * the band split of the mid plane (BandInfo, BandChunk) and RoundArgs,
@@ -40,7 +40,7 @@ struct CorrectionState {
     int steps_done;
 };
 // What a call's back half reads and writes once round 0 of the level correction has been launched: the correction
-// state and the reference's two scalars.  One per handle (mgx.hip, mgx_handle::back), like y and mid, not one per
+// state and the reference's two scalars.  One per handle (handle.h, mgx_handle::back), like y and mid, not one per
 // call context: round 0's launch (k_finalize_scalars where there are no rounds) copies the state the front half reset
 // and the two scalars out of the context, and every launch behind it works here.  The context is then free for the
 // front half of the next call but one.
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void k_correction_round(RoundArgs a) {
     if (a.lim_published) {
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.lim_words; i += (long long)gridDim.x * 256)
             a.lim_published[i] = ~0ull;
-        if (blockIdx.x == 0 && threadIdx.x == 0) a.lim_ticket[0] = a.lim_ticket[2] = 0;      // ticket and "gave up" (mgx.hip run_limiter); a raised error sticks
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.lim_ticket[0] = a.lim_ticket[2] = 0;      // ticket and "gave up" (run_limiter.h run_limiter); a raised error sticks
     }
     // this workgroup's slice of the band buffer, one compacted list per wave
     float* wave_band = bc.lists + wave * bc.wave_cap;
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256) void k_correction_tail(RoundArgs a, int groups
     if (a.lim_published) {
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.lim_words; i += (long long)gridDim.x * 256)
             a.lim_published[i] = ~0ull;
-        if (blockIdx.x == 0 && threadIdx.x == 0) a.lim_ticket[0] = a.lim_ticket[2] = 0;      // ticket and "gave up" (mgx.hip run_limiter); a raised error sticks
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.lim_ticket[0] = a.lim_ticket[2] = 0;      // ticket and "gave up" (run_limiter.h run_limiter); a raised error sticks
     }
     TAIL_STAMP(1);
     if ((int)blockIdx.x == total) {                                      // uniform: the extra workgroup decides

@@ -136,7 +136,7 @@ inline void backoff(int) {}
 #endif
 // How long a wait for another workgroup's word may last.  Nothing a chunk waits for takes longer than the kernel
 // itself (hundreds of microseconds); the bound exists so that a word that never comes -- the failure the handle
-// recovers from, mgx.hip check_device_error -- costs a bounded time and never hangs the GPU.  It is a TIME (the
+// recovers from, device_errors.h check_device_error -- costs a bounded time and never hangs the GPU.  It is a TIME (the
 // constant 100 MHz counter), not a poll count: 50 ms, looked at every 256 polls (~0.2 ms: a wait that ends as waits
 // do never gets there), and a waiter also gives up as soon as any other has (`gave_up`, a word in DEVICE memory:
 // the launch is lost whatever this chunk does), so a lost launch ends about 50 ms after its first waiter started --

@@ -1,0 +1,237 @@
+// libmgx.so's device-free part (mgx_policy.h): plain C++, no HIP.
+#include "mgx_policy.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "host_params.h"
+
+namespace mgx {
+
+// ---------------------------------------------------------------------------
+// errors
+// ---------------------------------------------------------------------------
+thread_local std::string g_error;
+int fail(int code, const std::string& msg) {
+    g_error = msg;
+    return code;
+}
+
+// The one range check of fft_size: a power of two in [8, max].  Each caller words its refusals itself, and says with
+// `code_above` whether a size above `max` is a bad argument or not implemented.
+static int check_fft_size(int fft_size, int max, const char* not_a_power, const char* below, int code_above,
+                          const char* above) {
+    if (ilog2_exact(fft_size) < 0) return fail(MGX_ERR_ARGUMENT, not_a_power);
+    if (fft_size < 8) return fail(MGX_ERR_ARGUMENT, below);
+    if (fft_size > max) return fail(code_above, above);
+    return 0;
+}
+
+int check_config(const mgx_config* c) {
+    if (!c) return fail(MGX_ERR_ARGUMENT, "config is null");
+    if (c->internal_sample_rate <= 0) return fail(MGX_ERR_ARGUMENT, "internal_sample_rate must be positive");
+    /* (below 8: defaults.py:110-112 lets 2 and 4 through; match_frequencies.py:45-58 then fails) */
+    MGX_TRY(check_fft_size(c->fft_size, 65536, "fft_size must be a power of two",
+                           "fft_size below 8: the reference's own cubic interpolation of the matching curve "
+                           "needs at least four points per side and fails there",
+                           MGX_ERR_UNSUPPORTED,
+                           "fft_size above 65536 is not implemented "
+                           "(an analysis segment is one, two or four transforms that fit one CU's LDS)"));
+    if (c->rms_correction_steps < 0) return fail(MGX_ERR_ARGUMENT, "rms_correction_steps must not be negative");
+    if (c->rms_correction_steps > 4096)      /* (a flag word per round and summing workgroup: 4 MB at 4096) */
+        return fail(MGX_ERR_UNSUPPORTED, "more than 4096 rms_correction_steps are not implemented");
+    if (c->lowess_it < 0 || c->lowess_it > 64) return fail(MGX_ERR_ARGUMENT, "lowess_it outside [0, 64]");
+    if (!(c->threshold > c->min_value && c->threshold < 1.0 && c->min_value > 0.0))
+        return fail(MGX_ERR_ARGUMENT, "threshold/min_value out of range (defaults.py:93-99)");
+    if (!(c->max_piece_size > c->fft_size)) return fail(MGX_ERR_ARGUMENT, "max_piece_size must exceed fft_size samples");
+    return 0;
+}
+
+// Kernels address a track through a buffer view with 32-bit byte offsets (mgx_hd.h MemView): 8 bytes
+// per frame plus the look-ahead of a convolution block must stay below 4 GiB.  That is 3.3 hours at
+// 44.1 kHz; the reference stops at max_length = 15 minutes by default (defaults.py, checker.py:58).
+int check_length(long long n) {
+    const long long max_frames = (0xfffffff0ll >> 3) - (1 << 16);
+    if (n > max_frames) return fail(MGX_ERR_UNSUPPORTED, "tracks longer than 536 million frames are not implemented");
+    return 0;
+}
+
+FirDesignParams fir_design_params(const mgx_config& c) {
+    return FirDesignParams{c.fft_size, c.internal_sample_rate, c.lin_log_oversampling, c.lowess_frac,
+                           c.lowess_it, c.lowess_delta, c.min_value};
+}
+
+void loudness_fill(const LoudnessGated& g, int64_t nsub, int S, mgx_loudness_report* report) {
+    report->integrated = g.integrated;
+    report->range = g.range;
+    report->momentary_max = g.momentary_max;
+    report->short_term_max = g.short_term_max;
+    report->sub_blocks = nsub;
+    report->sub_block_frames = S;
+    report->reserved = 0;
+}
+
+// the arguments mgx_delivery_gain and mgx_deliver share
+int deliver_format_check(int32_t bits, int32_t dither) {
+    if (bits != 0 && bits != 16 && bits != 24 && bits != 32)
+        return fail(MGX_ERR_ARGUMENT, "bits: a delivery is float32 (0) or 16, 24 or 32-bit PCM");
+    if (dither < 0 || dither > 2) return fail(MGX_ERR_ARGUMENT, "dither: 0 (none), 1 (TPDF) or 2 (high-passed TPDF)");
+    if (dither != 0 && (bits == 0 || bits == 32))
+        return fail(MGX_ERR_ARGUMENT, "dither: only 16 and 24-bit deliveries are dithered");
+    return 0;
+}
+
+// the numerator of g_peak: the linear ceiling less the quantiser's head-room (mgx_delivery_limit_step's ceiling is the same number)
+static int delivery_room(const mgx_delivery* delivery, double* room_out) {
+    // A: the most the meter's interpolator makes of errors of magnitude 1 -- the largest per-phase sum of |taps|
+    double taps[49], A = 0.0;
+    loudness_true_peak_taps(taps);
+    for (int p = 0; p < 4; ++p) {
+        double sum = 0.0;
+        for (int k = p; k < 49; k += 4) sum += std::fabs(taps[k]);
+        A = std::max(A, sum);
+    }
+    const double e = delivery->bits == 0 ? 0.0 : (delivery->dither ? 1.5 : 0.5);
+    const double margin = delivery->bits == 0 ? 0.0 : A * e / std::ldexp(1.0, delivery->bits - 1);
+    const double room = std::pow(10.0, delivery->ceiling_dbtp / 20.0) - margin;
+    if (!(room > 0.0))
+        return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: lower than the quantiser's own head-room at this width");
+    *room_out = room;
+    return 0;
+}
+
+}  // namespace mgx
+
+using namespace mgx;
+
+// ---------------------------------------------------------------------------
+// C ABI: the entry points that need no device
+// ---------------------------------------------------------------------------
+extern "C" {
+
+int mgx_version(void) { return 106; }
+const char* mgx_last_error(void) { return g_error.c_str(); }
+
+int mgx_config_default(mgx_config* c) {
+    if (!c) return fail(MGX_ERR_ARGUMENT, "config is null");
+    std::memset(c, 0, sizeof(*c));
+    c->internal_sample_rate = 44100;
+    c->fft_size = 4096;
+    c->lin_log_oversampling = 4;
+    c->rms_correction_steps = 4;
+    c->max_piece_size = 15.0 * 44100;
+    c->threshold = (32768.0 - 61.0) / 32768.0;
+    c->min_value = 1e-6;
+    c->lowess_frac = 0.0375;
+    c->lowess_it = 0;
+    c->lowess_delta = 0.001;
+    c->attack_ms = 1.0;
+    c->hold_ms = 1.0;
+    c->release_ms = 3000.0;
+    c->attack_filter_coefficient = -2.0;
+    c->hold_filter_order = 1;
+    c->release_filter_order = 1;
+    c->hold_filter_coefficient = 7.0;
+    c->release_filter_coefficient = 800.0;
+    return 0;
+}
+
+int mgx_design_fir(const mgx_config* cfg, const double* avg_target, const double* avg_reference, double* taps,
+                   double* curve_raw, double* curve_smooth) {
+    if (!cfg || !avg_target || !avg_reference || !taps) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const char* const refusal = "bad fft_size";                 // (no upper bound: the host design has none)
+    MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
+    if (cfg->lowess_it < 0 || cfg->lowess_it > 64) return fail(MGX_ERR_ARGUMENT, "lowess_it outside [0, 64]");
+    design_fir(avg_target, avg_reference, fir_design_params(*cfg), taps, curve_raw, curve_smooth);
+    return 0;
+}
+
+int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_rate, mgx_loudness_report* report) {
+    if (!report || count < 0 || (count > 0 && !sub_energy)) return fail(MGX_ERR_ARGUMENT, "null argument or negative count");
+    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "loudness is metered at sample rates of 8000 Hz and above");
+    const int S = (sample_rate + 5) / 10;
+    loudness_fill(loudness_gate(sub_energy, count, S), count, S, report);
+    return 0;
+}
+
+int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* measured, mgx_delivery_result* result) {
+    if (!delivery || !measured || !result) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(deliver_format_check(delivery->bits, delivery->dither));
+    const double target = delivery->target_lufs, ceiling = delivery->ceiling_dbtp;
+    const double integrated = measured->integrated, peak = measured->true_peak;
+    if (std::isinf(target)) return fail(MGX_ERR_ARGUMENT, "target_lufs: must be finite (NaN: no target)");
+    if (std::isinf(ceiling)) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: must be finite (NaN: no ceiling)");
+    if (ceiling > 0.0) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: a ceiling above 0 dBTP would clip");
+    if (!std::isfinite(peak) || peak < 0.0) return fail(MGX_ERR_ARGUMENT, "true_peak: the measured peak is negative or not finite");
+    if (std::isnan(integrated) || integrated == INFINITY)
+        return fail(MGX_ERR_ARGUMENT, "integrated: the measured loudness is NaN or +infinity");
+    const bool has_loud = !std::isnan(target) && std::isfinite(integrated);
+    const double g_loud = has_loud ? std::pow(10.0, (target - integrated) / 20.0) : 1.0;
+    double g_peak = INFINITY;
+    if (!std::isnan(ceiling)) {
+        double room;
+        MGX_TRY(delivery_room(delivery, &room));
+        if (peak > 0.0) g_peak = room / peak;
+    }
+    const double gain = std::min(g_loud, g_peak);
+    result->gain = gain;
+    result->achieved_lufs = std::isfinite(integrated) ? integrated + 20.0 * std::log10(gain) : -INFINITY;
+    result->achieved_true_peak = gain * peak;
+    const bool by_peak = g_peak < g_loud;
+    result->shortfall_lu = by_peak && has_loud ? 20.0 * std::log10(g_loud / gain) : 0.0;
+    result->limited_by = by_peak ? 2 : (has_loud ? 1 : 0);
+    result->reserved = 0;
+    return 0;
+}
+
+int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_report* rendering, int32_t passes,
+                            const double* pre_gain_db, const double* integrated, int32_t max_passes, double tolerance_lu,
+                            mgx_delivery_limit_plan* next) {
+    if (!delivery || !rendering || !next) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (max_passes < 1 || max_passes > MGX_LIMIT_PASSES_MAX)
+        return fail(MGX_ERR_ARGUMENT, "max_passes: outside [1, " + std::to_string(MGX_LIMIT_PASSES_MAX) + "]");
+    if (!(tolerance_lu >= 0.0) || std::isinf(tolerance_lu)) return fail(MGX_ERR_ARGUMENT, "tolerance_lu: negative or not finite");
+    if (passes < 0 || passes > max_passes) return fail(MGX_ERR_ARGUMENT, "passes: outside [0, max_passes]");
+    if (passes > 0 && (!pre_gain_db || !integrated)) return fail(MGX_ERR_ARGUMENT, "pre_gain_db / integrated: null with passes run");
+    if (std::isnan(delivery->ceiling_dbtp)) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: a limiter needs a ceiling");
+    mgx_delivery_result linear;
+    MGX_TRY(mgx_delivery_gain(delivery, rendering, &linear));
+    next->run = 0;
+    next->reserved = 0;
+    next->pre_gain_db = passes > 0 ? pre_gain_db[passes - 1] : 0.0;
+    MGX_TRY(delivery_room(delivery, &next->ceiling));
+    const double target = delivery->target_lufs;
+    const bool has_target = !std::isnan(target) && std::isfinite(rendering->integrated);
+    if (passes == 0) {
+        if (linear.limited_by != 2) return 0;                  // the linear policy reaches what was asked for
+        next->run = 1;
+        next->pre_gain_db = has_target ? target - rendering->integrated : 0.0;
+        return 0;
+    }
+    const double p = pre_gain_db[passes - 1], loud = integrated[passes - 1];
+    if (std::isnan(p) || std::isnan(loud) || loud == INFINITY)
+        return fail(MGX_ERR_ARGUMENT, "pre_gain_db / integrated: NaN or +infinity in the passes run");
+    if (!has_target || target - loud <= tolerance_lu || passes == max_passes || std::isinf(loud)) return 0;
+    double slope = 1.0;
+    if (passes >= 2) {
+        const double dp = p - pre_gain_db[passes - 2], dl = loud - integrated[passes - 2];
+        if (dp == 0.0 || !(dl / dp >= 0.1)) return 0;           // more pre-gain buys no loudness: a steady tone under a ceiling
+        slope = std::min(dl / dp, 1.0);
+    }
+    next->run = 1;
+    next->pre_gain_db = p + (target - loud) / slope;
+    return 0;
+}
+
+// ---- reference profiles -------------------------------------------------------
+int mgx_profile_bytes(const mgx_config* cfg, size_t* bytes) {
+    if (!cfg || !bytes) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const char* const refusal = "fft_size must be a power of two in [8, 65536]";
+    MGX_TRY(check_fft_size(cfg->fft_size, 65536, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
+    *bytes = sizeof(mgx_profile_header) + (size_t)2 * (cfg->fft_size / 2 + 1) * sizeof(double);
+    return 0;
+}
+
+}  // extern "C"

@@ -151,7 +151,7 @@ __device__ __forceinline__ int opaque(int v) {
 // A limiter look-back that expires (limiter_kernel.h) means a lost word: the
 // audio is wrong and the call fails.  An expired wait of k_correction_tail means its workgroups were not resident
 // together (another process's kernels held the compute units): the host then runs the rounds again as one launch
-// each, which wait for nobody (mgx.hip, check_device_error).  DEVICE_ERROR_INPUT is not a wait at all: the level
+// each, which wait for nobody (device_errors.h, check_device_error).  DEVICE_ERROR_INPUT is not a wait at all: the level
 // analysis met a NaN or an infinity (k_match_curve), where the reference raises.  Nor is DEVICE_ERROR_PROFILE: a reference
 // profile whose header does not fit the call's Config (profile_kernels.h); its word holds WHICH field, not a 1.
 constexpr int DEVICE_ERROR_LOOKBACK = 1, DEVICE_ERROR_TAIL = 2, DEVICE_ERROR_INPUT = 4, DEVICE_ERROR_PROFILE = 8;
@@ -171,7 +171,7 @@ constexpr int DEVICE_ERROR_SLOT_LOOKBACK = 0, DEVICE_ERROR_SLOT_TAIL = 1, DEVICE
 // into the XCD's L2; instruction fetch then finds it there.  (Every workgroup of the first generation doing so was
 // measured: the limiter lost 14 us to the wait; so was warming again every 16th or 64th workgroup of an XCD, in
 // case the streamed audio pushes the code out of the L2 again: +6 / +13 us.)  Sizes come from the code object's
-// symbol table (mgx.hip, code_sizes_from_library); zero = no warming.
+// symbol table (code_sizes.h, code_sizes_from_library; uploaded by mgx_create); zero = no warming.
 enum { CODE_ANALYZE = 0, CODE_MATCH_CURVE, CODE_CONV_PREP, CODE_CONV, CODE_ROUND, CODE_TAIL, CODE_LIMIT, CODE_KERNELS };
 constexpr int CODE_VARIANTS = 16;                                  // second index: log2 of the transform; 0 / 1 = 256 / 1024-block limiter
 constexpr int CODE_VARIANT_CONV_DELAY = 15;                        // [CODE_CONV][15]: k_conv_delay<14>

@@ -21,5 +21,20 @@ def build(force=False):
     return OUT
 
 
+# The library's device-free unit (csrc/mgx_policy.cpp) in a stand-alone program, with whatever extra flags (a
+# sanitizer's) the caller gives: mgx_design_fir brings in the host FIR design this file already builds, the loudness
+# gate and the delivery head-room bring in loudness_plan.cpp.
+POLICY_DRIVER = os.path.join(HERE, "emu_policy_driver")
+POLICY_SOURCES = [os.path.join(HERE, "emu_policy_driver.cpp")] + [
+    os.path.join(ROOT, "matchering_amd", "csrc", f) for f in ("mgx_policy.cpp", "loudness_plan.cpp", "fir_design.cpp", "fir_plan.cpp")]
+
+
+def build_policy_driver(out=POLICY_DRIVER, extra_flags=()):
+    cxx = os.environ.get("CXX", "g++")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-DMGX_HOST_EMU", "-Wall", "-ffp-contract=off", *extra_flags,
+                           "-o", out] + POLICY_SOURCES)
+    return out
+
+
 if __name__ == "__main__":
     print(build(force=True))

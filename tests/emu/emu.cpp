@@ -873,7 +873,7 @@ extern "C" int emu_design_fir_direct(const mgx_config* cfg, const double* avg_ta
     design_fir_direct(avg_target, avg_reference, p, taps, curve_raw, curve_smooth);
     return 0;
 }
-// The raw -> smooth operator in its two factors through the LOWESS anchors (mgx.hip build_fir_factors, fir_kernels.h
+// The raw -> smooth operator in its two factors through the LOWESS anchors (run_fir.h build_fir_factors, fir_kernels.h
 // k_fir_apply_a / k_fir_apply_b), with the phase functions the device kernels run: unit raw curves -> the anchors' fits
 // (A), unit fits -> the smooth curve (B), rows cut to the window above 1e-18 of their largest entry (k_fir_band), then
 // smooth = B (A raw) with bins 0 and 1 pinned.  Returns the windows' total sizes (in doubles) for the two factors.

@@ -54,7 +54,7 @@ def analysis_cases(fft):
         "prime_segments": dict(D=2, q=13, left=5, tail=0, spike=None, emu=True),
         "one_division": dict(D=1, q=5, left=3, tail=0, spike=None, emu=True),
     }
-    # More workgroups than the chip holds (choose_chunks in mgx.hip: at most CUs x workgroups-per-CU, the latter at
+    # More workgroups than the chip holds (choose_chunks in run_analysis.h: at most CUs x workgroups-per-CU, the latter at
     # most ANALYZE_MAX_WGS = 8 and at most what the LDS admits: 4 / 2 / 1 for 4096 / 8192 / 16384-point transforms):
     # D * q beyond that forces more than one segment per workgroup, and with q prime the s0/s1 split is uneven.
     if fft <= 256:
@@ -234,7 +234,7 @@ CONV_DIRECT_TILE = 1024                                  # small_fft_kernels.h
 
 
 def conv_route(taps):
-    """(route, hop in output frames, frames of one block) as run_conv in mgx.hip decides."""
+    """(route, hop in output frames, frames of one block) as run_conv in run_conv.h decides."""
     if taps <= 32:
         return "direct", CONV_DIRECT_TILE, CONV_DIRECT_TILE
     if taps == 4096:

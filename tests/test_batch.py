@@ -144,7 +144,7 @@ def test_gpu_limiters_of_two_handles_never_wait_for_each_other():
     larger than the chip holds at once (1024): left to themselves the two limiter launches would be resident together,
     each XCD's slots full of one launch's waiting workgroups while the other launch's lowest chunk cannot start there
     (k_limit deals chunks by workgroup number).  The library chains limiter launches of a device through an event per
-    handle (mgx.hip, LimiterChain): every call completes, no look-back wait expires, results equal a lone run's."""
+    handle (handle.h, LimiterChain): every call completes, no look-back wait expires, results equal a lone run's."""
     from matchering_amd.device import Device
 
     cfg = mg.Config()

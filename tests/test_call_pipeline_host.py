@@ -2,7 +2,7 @@
 
 The planner says, for every ``mgx_master`` call, which per-call context it uses and which event waits order its front
 half (analysis, FIR design, filter spectra -- possibly on the front stream) against the rest.  The tests execute its
-plans on a model of two in-order streams with events, exactly as ``queue_master`` in mgx.hip does, and check the
+plans on a model of two in-order streams with events, exactly as ``queue_master`` in master_call.h does, and check the
 invariant rather than the implementation: any two operations that touch the same context, the same back-half buffers
 or overlapping user ranges, where at least one of them writes, are ordered by a chain of "same stream" and "event
 wait" edges (or by a host synchronisation in between).
@@ -55,7 +55,7 @@ BACK = ("back",)                # y, mid, band, block_peak, the limiter's words:
 
 
 class Model:
-    """Two in-order streams, events, host synchronisations; the planner drives it as mgx.hip executes its plans."""
+    """Two in-order streams, events, host synchronisations; the planner drives it as master_call.h executes its plans."""
 
     def __init__(self, lib):
         self.lib = lib

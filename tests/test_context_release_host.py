@@ -1,6 +1,6 @@
 """The early release of a call's context on the model of tests/test_call_pipeline_host.py, without a GPU.
 
-The back half of a master call is two operations here, as mgx.hip queues it:
+The back half of a master call is two operations here, as master_call.h queues it:
 
   A = convolution + round 0 of the level correction: reads the context and the target, writes the handle's back buffers
       (y, mid, the band lists, the back state);

@@ -405,7 +405,7 @@ def test_fir_design_phases_with_lowess_iterations(emu, it):
 
 @pytest.mark.parametrize("fft,sr", [(256, 44100), (1024, 96000)])
 def test_fir_operator_in_two_factors_through_the_lowess_anchors(emu, fft, sr):
-    """raw -> smooth as B (A raw) (mgx.hip build_fir_factors; k_fir_apply_a / k_fir_apply_b), built and applied on the
+    """raw -> smooth as B (A raw) (run_fir.h build_fir_factors; k_fir_apply_a / k_fir_apply_b), built and applied on the
     host with the device's own phase functions: equal to the chain run on the curve itself (emu_design_fir) and to the
     oracle's smoothing (match_frequencies.py:45-75) to float64 rounding, bins 0 and 1 pinned, and both factors banded
     (their windows a small part of anchors x bins)."""

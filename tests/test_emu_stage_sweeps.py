@@ -91,7 +91,7 @@ def test_analysis_of_mono_and_hard_panned_tracks(emu, fft, kind):
 
 # ---- B. convolution -------------------------------------------------------------------------------------------------
 def emu_convolve(emu, x, hm, hs, gain, taps):
-    """The form run_conv (mgx.hip) takes for this tap count."""
+    """The form run_conv (run_conv.h) takes for this tap count."""
     n = x.shape[0]
     x = np.ascontiguousarray(x, dtype=np.float32)
     y, ymid = np.zeros((n, 2), dtype=np.float32), np.zeros(n, dtype=np.float32)
@@ -172,7 +172,7 @@ def emu_limit(emu, x, cfg):
 
 
 def test_limiter_geometry_export_matches_what_the_kernels_are_built_for(emu):
-    """The geometries launch_limiter_256 (mgx.hip) has instantiations for, from the library's own rule."""
+    """The geometries launch_limiter_256 (run_limiter.h) has instantiations for, from the library's own rule."""
     import matchering_amd as mg
 
     g = limiter_geometry(emu, mg.Config())

@@ -197,7 +197,7 @@ def test_limiter_first_and_last_64_frames(geometry, name, kind):
 
 
 def test_limiter_refuses_seven_frames():
-    """limiter_args (mgx.hip) takes eight frames at least: the lower edge of the sweep is the library's own."""
+    """limiter_args (run_limiter.h) takes eight frames at least: the lower edge of the sweep is the library's own."""
     import matchering_amd as mg
     from matchering_amd import kernels
     from matchering_amd._native import MgxError
