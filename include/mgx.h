@@ -216,6 +216,21 @@ int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels,
 int mgx_resample_plan(mgx_handle* h, int32_t rate_in, int32_t rate_out, void** weights_dev, int32_t* phases,
                       int32_t* row_entries, int64_t* designed);
 
+/* Sample-rate conversion of a delivery: (n, 2) float32 frames in HBM at rate_in -> (n_out, 2) float32 frames in HBM at
+ * rate_out, n_out = int(n * (rate_out / rate_in)); queued on the handle's stream, waits for nothing.  Each output is the
+ * sum mgx_resample computes for the same frames -- the same plan rows, float64 samples and weights, explicit fma in tap
+ * order, one rounding to float32 at the store -- so the result is bit-identical to mgx_resample(..., channels = 2, ...)
+ * on the same input; the kernel (csrc/convert_rate_kernel.h) loads each weight once for up to 8 outputs a whole number
+ * of periods apart.  The weights are those of mgx_resample, shared: whichever entry point meets a rate pair first on a
+ * handle designs and uploads them, mgx_resample_plan reports both.  The contract is mgx_resample's: with out_dev ==
+ * NULL the call only reports n_out and the refusal (and needs no handle).  MGX_ERR_ARGUMENT: a rate <= 0, rate_in ==
+ * rate_out, out_capacity_frames < n_out.  MGX_ERR_UNSUPPORTED: what mgx_resample refuses for its ratio -- more than
+ * 4096 phases (44100 -> 44056), 256 outputs reaching more than 7680 input frames, more than 64 MiB of weights -- and
+ * more than 500 million frames on either side; a delivery has no host path to fall back to.  n_out == 0 succeeds and
+ * launches nothing. */
+int mgx_convert_rate(mgx_handle* h, const float* x_dev, int64_t n, int32_t rate_in, int32_t rate_out, float* out_dev,
+                     int64_t out_capacity_frames, int64_t* n_out);
+
 /* Album mode (the use of the FIR broadcast): stages.main with the matching-EQ FIR
  * GIVEN instead of designed from this pair's spectra -- `fir_dev` = [2][fft_size] float32 in HBM, mid
  * taps then side taps, e.g. the table mgx_last_fir returns on the rank that designed it, after

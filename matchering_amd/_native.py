@@ -197,6 +197,8 @@ SYMBOLS = {
                                     ctypes.c_int64, c_int64_p]),
     "mgx_resample_plan": (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_VP), c_int32_p, c_int32_p,
                                          c_int64_p]),
+    "mgx_convert_rate": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _VP, ctypes.c_int64,
+                                        c_int64_p]),
     "mgx_window_energy": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_double_p,
                                          ctypes.c_int64, c_int64_p]),
     "mgx_loudness": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport), c_double_p,

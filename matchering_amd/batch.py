@@ -28,8 +28,9 @@ and on a node with 8 GPUs::
 
 ``jobs.json`` is a list of ``{"target": path, "reference": path, "results": [{"file": path,
 "subtype": "PCM_16", "use_limiter": true, "normalize": true, "delivery": {"loudness": -14, "true_peak": -1,
-"dither": "tpdf_hp", "seed": 0, "limiter": true}}, ...]}`` (``"delivery"`` and each of its keys optional: ``delivery.Delivery``;
-``"limiter"``: ``true`` or the fields of ``delivery.TruePeakLimiter``); in place of ``"reference"`` a job may name a
+"dither": "tpdf_hp", "seed": 0, "limiter": true, "sample_rate": 48000}}, ...]}`` (``"delivery"`` and each of its keys
+optional: ``delivery.Delivery``; ``"limiter"``: ``true`` or the fields of ``delivery.TruePeakLimiter``; ``"sample_rate"``: the
+rate of that file in Hz, converted on the device, default the Config's internal rate); in place of ``"reference"`` a job may name a
 ``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
 list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).
 """
@@ -562,7 +563,7 @@ def _save_job(job, triple, config, deliveries=None):
     for wanted in plain_results(job["results"]):
         chosen = result if wanted.use_limiter else (normalized if wanted.normalize else plain)
         save(wanted.file, chosen, config.internal_sample_rate, wanted.subtype)
-    if deliveries:
+    if deliveries:                                 # (each at its delivery's own rate)
         write_deliveries(job["results"], deliveries, config.internal_sample_rate)
 
 
@@ -585,6 +586,10 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     for i in mine:
         if not jobs[i].get("results"):
             raise RuntimeError("The result list is empty")
+        # (a delivery rate the device converter refuses is a ValueError here, before a file is read)
+        from .delivery import DeliveryRequest
+
+        DeliveryRequest.for_results(jobs[i]["results"]).check_rates(config.internal_sample_rate)
     device_index = local if device_index is None else device_index
     savers = []
     shared_keys = set()

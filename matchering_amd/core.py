@@ -180,7 +180,7 @@ def _same_file(a, b):
 
 def _write_results(results, renderings, sample_rate, deliveries=None):
     """One file per Result, each from the rendering it asked for (core.py:95-108); a Result with a delivery from the
-    array ``stages.main`` left in the ``DeliveryRequest``."""
+    array ``stages.main`` left in the ``DeliveryRequest``, at its delivery's own rate."""
     limited, plain, normalized = renderings
     for item in plain_results(results):
         audio = limited if item.use_limiter else (normalized if item.normalize else plain)
@@ -201,6 +201,8 @@ def process(target: str, reference: str, results: list, config: Config = None,
     if not results:
         raise RuntimeError("The result list is empty")
     temp_folder = config.temp_folder or get_temp_folder(results)
+    # (a delivery rate the device converter refuses is a ValueError here, before a file is read)
+    DeliveryRequest.for_results(results).check_rates(config.internal_sample_rate)
 
     profile = _as_profile(reference, config)
     if profile is not None:

@@ -24,6 +24,7 @@
 #include "loudness_kernel.h"
 #include "loudness_plan.h"
 #include "mgx_kernels.h"
+#include "convert_rate_kernel.h"
 #include "resample_kernel.h"
 #include "resample_plan.h"
 #include "deliver_kernel.h"            // (behind every other kernel: it moves none of them in the code object)
@@ -632,6 +633,61 @@ int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels,
         hipLaunchKernelGGL(k_resample<2>, dim3(grid), dim3(RESAMPLE_BLOCK), lds, h->stream, a);
     else
         hipLaunchKernelGGL(k_resample<1>, dim3(grid), dim3(RESAMPLE_BLOCK), lds, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mgx_convert_rate(mgx_handle* h, const float* x_dev, int64_t n, int32_t rate_in, int32_t rate_out, float* out_dev,
+                     int64_t out_capacity_frames, int64_t* n_out) {
+    // everything that depends on the numbers alone is settled before the handle is touched (mgx_resample's contract)
+    if (!n_out) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (rate_in <= 0 || rate_out <= 0) return fail(MGX_ERR_ARGUMENT, "sample rates must be positive");
+    if (rate_in == rate_out) return fail(MGX_ERR_ARGUMENT, "the frames are at the requested rate already");
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
+    ResampleGeometry g;
+    std::string why;
+    if (resample_geometry(rate_in, rate_out, &g, &why) != 0)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_convert_rate " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " Hz: " + why);
+    const int64_t frames = resample_length(n, rate_in, rate_out);
+    if (n > RESAMPLE_FRAMES_MAX || frames > RESAMPLE_FRAMES_MAX)
+        return fail(MGX_ERR_UNSUPPORTED, "mgx_convert_rate: tracks of more than 500 million frames are not converted here");
+    *n_out = frames;
+    if (!out_dev) return 0;                                     // the caller asked for the length only
+    if (!h || !x_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (out_capacity_frames < frames) return fail(MGX_ERR_ARGUMENT, "the output holds fewer frames than the conversion gives");
+    if (frames == 0) return 0;
+    MGX_TRY(open_main(h));
+    // (mgx_resample's cache: whichever of the two meets a rate pair first designs and uploads it, once for both)
+    mgx_handle::ResampleDev& dev = h->resample_plans[{rate_in, rate_out}];
+    if (!dev.matrix.p) {
+        dev.plan = resample_design(rate_in, rate_out);
+        if (!dev.plan) return fail(MGX_ERR_UNSUPPORTED, "mgx_convert_rate: no plan for these rates");
+        dev.host = resample_device_matrix(*dev.plan);
+        MGX_TRY(ensure(h, dev.matrix, dev.host.size() * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(dev.matrix.p, dev.host.data(), dev.host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        ++h->resample_designs;
+    }
+    const ConvertRateTiling tiling = convert_rate_tiling(g);
+    ConvertRateArgs a;
+    a.x = x_dev;
+    a.n = n;
+    a.w = (const double*)dev.matrix.p;
+    a.L = g.L;
+    a.M = g.M;
+    a.W = g.W;
+    a.out = out_dev;
+    a.n_out = frames;
+    a.S = tiling.S;
+    a.hop = tiling.S / g.L * g.M;
+    const long long tile = (long long)tiling.P * tiling.S;
+    const unsigned grid = (unsigned)((frames + tile - 1) / tile);
+    const size_t lds = (size_t)tiling.span * sizeof(float2);
+    switch (tiling.P) {
+        case 8: hipLaunchKernelGGL(k_convert_rate<8>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
+        case 4: hipLaunchKernelGGL(k_convert_rate<4>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
+        case 2: hipLaunchKernelGGL(k_convert_rate<2>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
+        default: hipLaunchKernelGGL(k_convert_rate<1>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -21,6 +21,12 @@ A delivery may carry a ``TruePeakLimiter``: where the ceiling binds -- and only 
 unchanged and ``shortfall_lu`` says what is still missing.
 
     mg.pcm16("club.wav", delivery=mg.Delivery(loudness=-9.0, true_peak=-1.0, dither="tpdf_hp", limiter=mg.TruePeakLimiter()))
+
+A delivery may name a ``sample_rate``: the rendering is converted to it in HBM (``mgx_convert_rate``) BEFORE all of the
+above, which then runs on the converted frames at that rate, so the ceiling holds for the file at the rate it is written
+at.
+
+    mg.pcm24("video.wav", delivery=mg.Delivery(loudness=-14.0, true_peak=-1.0, sample_rate=48000))
 """
 
 import ctypes
@@ -37,6 +43,7 @@ LIMITED_BY = (None, "loudness", "true_peak")
 LOOKAHEAD_MAX = 2048                # frames: TPL_LOOKAHEAD_MAX (csrc/tp_limit_kernel.h)
 RELEASE_MAX = 2 ** 22               # frames
 PASSES_MAX = 16                     # MGX_LIMIT_PASSES_MAX
+RATE_MIN = 8000                     # Hz: the meter's floor (mgx_loudness, include/mgx.h)
 
 
 @dataclass(frozen=True)
@@ -93,13 +100,17 @@ class Delivery:
     """What a result is to meet.  ``loudness``: integrated loudness in LUFS, ``true_peak``: the ceiling in dBTP (at most
     0), either may be None; ``dither``: None, "tpdf" or "tpdf_hp" (high-passed TPDF), for 16 and 24-bit files;
     ``seed``: the dither generator's key -- the same seed writes the same file; ``limiter``: a ``TruePeakLimiter`` to run
-    where the ceiling keeps the linear gain under the target (it needs ``true_peak``), None for the linear gain alone."""
+    where the ceiling keeps the linear gain under the target (it needs ``true_peak``), None for the linear gain alone;
+    ``sample_rate``: the rate of the written file in Hz -- the rendering is converted in HBM (``mgx_convert_rate``)
+    before it is measured, so the loudness and the ceiling hold for the file at THAT rate -- None for the Config's
+    internal rate."""
 
     loudness: float = None
     true_peak: float = None
     dither: str = None
     seed: int = 0
     limiter: TruePeakLimiter = None
+    sample_rate: int = None
 
     def __post_init__(self):
         for name in ("loudness", "true_peak"):
@@ -117,6 +128,15 @@ class Delivery:
                 raise ValueError(f"Delivery: limiter must be a TruePeakLimiter or None, got {self.limiter!r}")
             if self.true_peak is None:
                 raise ValueError("Delivery: a limiter needs a true_peak ceiling to hold")
+        if self.sample_rate is not None:
+            if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int):
+                raise ValueError(f"Delivery: sample_rate must be an integer number of Hz or None, got {self.sample_rate!r}")
+            if self.sample_rate < RATE_MIN:
+                raise ValueError(f"Delivery: sample_rate must be at least {RATE_MIN} Hz, got {self.sample_rate!r}")
+
+    def rate(self, internal_rate):
+        """The rate of the written file: ``sample_rate``, or the Config's internal rate where it is None."""
+        return int(internal_rate) if self.sample_rate is None else self.sample_rate
 
     def check_subtype(self, subtype):
         """The error ``Result`` raises at construction for a width this delivery cannot be written at."""
@@ -132,13 +152,13 @@ class Delivery:
 
     @classmethod
     def from_json(cls, entry):
-        """``{"loudness": ..., "true_peak": ..., "dither": ..., "seed": ..., "limiter": ...}`` of a batch job (every key
-        optional; ``"limiter"``: ``true`` for ``TruePeakLimiter()``, or an object with its fields)."""
+        """``{"loudness": ..., "true_peak": ..., "dither": ..., "seed": ..., "limiter": ..., "sample_rate": ...}`` of a
+        batch job (every key optional; ``"limiter"``: ``true`` for ``TruePeakLimiter()``, or an object with its fields)."""
         if isinstance(entry, cls):
             return entry
         if not isinstance(entry, dict):
-            raise ValueError(f"a delivery is an object with loudness / true_peak / dither / seed / limiter, got {entry!r}")
-        unknown = set(entry) - {"loudness", "true_peak", "dither", "seed", "limiter"}
+            raise ValueError(f"a delivery is an object with loudness / true_peak / dither / seed / limiter / sample_rate, got {entry!r}")
+        unknown = set(entry) - {"loudness", "true_peak", "dither", "seed", "limiter", "sample_rate"}
         if unknown:
             raise ValueError(f"delivery: unknown keys {sorted(unknown)}")
         if entry.get("limiter") in (None, False):
@@ -150,6 +170,9 @@ class Delivery:
 class Delivered:
     """What became of one delivery: ``mgx_delivery_result``'s fields, the measurement they were derived from and the
     request.  ``achieved_lufs`` / ``achieved_true_peak`` (linear) are predicted from the measurement of the rendering.
+    ``sample_rate`` / ``frames``: the rate and length of the written file (None / None from ``delivery_gain`` alone, which
+    sees a measurement and no audio); for a delivery at another rate than the internal one ``measured`` is the
+    measurement of the CONVERTED rendering at the delivery's rate -- the one the gain was derived from.
     Where the delivery's limiter ran (``limiter_passes`` > 0) ``measured`` is still the rendering's measurement, ``limited``
     the one of the last pass's frames -- which ``gain`` and the achieved values refer to -- ``pre_gain_db`` that pass's
     pre-gain and ``max_reduction_db`` its deepest gain reduction (a negative number of dB)."""
@@ -166,6 +189,9 @@ class Delivered:
     pre_gain_db: float = 0.0
     max_reduction_db: float = 0.0
     limited: Loudness = None
+    sample_rate: int = None
+    frames: int = None
+    internal_rate: int = None       # the rate of the rendering it was made from
 
     @property
     def gain_db(self):
@@ -180,6 +206,8 @@ class Delivered:
         text = (f"gain {self.gain_db:+.2f} dB: {self.achieved_lufs:.2f} LUFS, true peak {self.achieved_true_peak_db:.2f} dBTP "
                 f"({'float32' if self.bits == 0 else f'{self.bits} bit'}"
                 f"{'' if self.delivery.dither is None else ', ' + self.delivery.dither})")
+        if self.sample_rate is not None and self.sample_rate != self.internal_rate:
+            text += f" at {self.sample_rate} Hz"
         if self.limiter_passes > 0:
             text += (f"; limited in {self.limiter_passes} pass{'' if self.limiter_passes == 1 else 'es'}: pre-gain "
                      f"{self.pre_gain_db:+.2f} dB, at most {self.max_reduction_db:.2f} dB of reduction")
@@ -263,6 +291,19 @@ class DeliveryRequest:
                 request.add(item.file, rendering_of(item), item.subtype, item.delivery)
         return request
 
+    def check_rates(self, internal_rate, frames=0):
+        """``{rate: frames of a rendering of ``frames`` frames converted to it}`` for every delivery rate other than
+        ``internal_rate``; ``ValueError`` naming both rates and the library's reason for a pair ``mgx_convert_rate``
+        refuses.  Needs no GPU (the entry point's device-free form): ``process`` calls it before any audio is loaded."""
+        from .device import delivery_length
+
+        lengths = {}
+        for _, _, _, delivery in self.items:
+            rate = delivery.rate(internal_rate)
+            if rate != internal_rate and rate not in lengths:
+                lengths[rate] = delivery_length(frames, internal_rate, rate)
+        return lengths
+
     def needs(self):
         """Which of ``main``'s three renderings the items are cut from."""
         return tuple(any(r == slot for _, r, _, _ in self.items) for slot in range(3))
@@ -282,8 +323,9 @@ def plain_results(results):
 
 
 def write_deliveries(results, request, sample_rate):
-    """One file per Result that carries a delivery, from the arrays ``stages.main`` left in ``request``; one log line
-    each: gain, achieved LUFS and dBTP, and the shortfall where the ceiling bound the loudness."""
+    """One file per Result that carries a delivery, from the arrays ``stages.main`` left in ``request``, each at its own
+    rate (``sample_rate``: the internal one, for the deliveries that name none); one log line each: gain, achieved LUFS
+    and dBTP, and the shortfall where the ceiling bound the loudness."""
     from .audio_io import save
     from .log import debug
 
@@ -291,4 +333,4 @@ def write_deliveries(results, request, sample_rate):
         if getattr(item, "delivery", None) is None:
             continue
         debug(f"delivery '{item.file}': {request.delivered[item.file]}")
-        save(item.file, request.arrays[item.file], sample_rate, item.subtype)
+        save(item.file, request.arrays[item.file], item.delivery.rate(sample_rate), item.subtype)

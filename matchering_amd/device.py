@@ -168,6 +168,18 @@ def converted_length(frames, channels, rate_in, rate_out):
     return n_out.value
 
 
+def delivery_length(frames, rate_in, rate_out):
+    """Frames ``mgx_convert_rate`` makes of a rendering for a delivery at ``rate_out``; ``ValueError`` naming both rates
+    and the library's reason for a pair it refuses (a delivery has no host route to fall back to).  Needs no GPU."""
+    n_out = ctypes.c_int64()
+    rc = library().mgx_convert_rate(None, None, int(frames), int(rate_in), int(rate_out), None, 0, ctypes.byref(n_out))
+    if rc == _native.ERR_UNSUPPORTED:
+        raise ValueError(f"a delivery at {rate_out} Hz cannot be made from {rate_in} Hz: "
+                         + library().mgx_last_error().decode("utf-8", "replace"))
+    check(rc)
+    return n_out.value
+
+
 def takes_resident(audio, rate, internal_rate):
     """Whether a loaded track goes to the GPU as its file holds it, to become (frames, 2) float32 at the internal
     rate there (``Device.track_frames``): one or two channels of samples float32 holds exactly -- int16, packed
@@ -358,6 +370,23 @@ class Device:
         try:
             check(lib.mgx_resample(self.handle, ctypes.c_void_p(ptr), int(frames), int(channels), int(rate_in),
                                    int(rate_out), ctypes.c_void_p(out.ptr), n_out.value, ctypes.byref(n_out)))
+        except Exception:
+            out.release()
+            raise
+        return DeviceFrames(out, n_out.value)
+
+    def convert_rate(self, buf, frames, rate_in, rate_out):
+        """(frames, 2) float32 in HBM at ``rate_in`` -> a new ``DeviceFrames`` of (n_out, 2) at ``rate_out``
+        (``mgx_convert_rate``: the deliveries' converter, bit-identical to ``resample_frames`` of two channels), queued on
+        this device's stream.  Raises ``MgxError`` with ``code == ERR_UNSUPPORTED`` for the ratios the library refuses."""
+        lib = library()
+        n_out = ctypes.c_int64()
+        check(lib.mgx_convert_rate(None, None, int(frames), int(rate_in), int(rate_out), None, 0, ctypes.byref(n_out)))
+        out = DeviceBuffer(self, max(n_out.value * 8, 1))
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        try:
+            check(lib.mgx_convert_rate(self.handle, ctypes.c_void_p(ptr), int(frames), int(rate_in), int(rate_out),
+                                       ctypes.c_void_p(out.ptr), n_out.value, ctypes.byref(n_out)))
         except Exception:
             out.release()
             raise

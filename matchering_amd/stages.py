@@ -93,7 +93,9 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # renditions of the renderings at a loudness target, under a true-peak ceiling, dithered (mgx_delivery_gain,
     # mgx_deliver), made while the renderings are still in HBM and left in the request; a rendering that only a delivery
     # names is computed but not returned, and ``loudness`` also receives ("delivered:" + key, delivery.Delivered).  A
-    # delivery that carries a limiter and whose ceiling binds is limited first (mgx_tp_limit, mgx_delivery_limit_step).)
+    # delivery that carries a limiter and whose ceiling binds is limited first (mgx_tp_limit, mgx_delivery_limit_step).  A
+    # delivery at another ``sample_rate`` than the internal one is made from the rendering converted to that rate in HBM
+    # (mgx_convert_rate) and measured there; the renderings returned, the previews and the other callbacks do not change.)
     dev = device if device is not None else default_device()
     target = _as_frames(target, "target")
     profile = reference if _is_profile(reference) else None
@@ -105,6 +107,9 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
         nr = reference.shape[0]
     n = target.shape[0]
     native = config.to_native()
+    if deliveries:
+        # (ValueError before anything reaches the GPU: a rate pair mgx_convert_rate refuses has no other route)
+        deliveries.check_rates(config.internal_sample_rate, n)
 
     debug_line()
     info(Code.INFO_MATCHING_LEVELS)
@@ -155,30 +160,49 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                         metered[slot] = dev.loudness(outs[slot], n, rate)
                         loudness(name, metered[slot])
             if deliveries:
+                from dataclasses import replace
+
                 from .delivery import DITHERS, SUBTYPE_BITS, delivery_gain
 
-                for key, slot, subtype, delivery in deliveries.items:
-                    if slot not in metered:
-                        metered[slot] = dev.loudness(outs[slot], n, rate)
-                    bits = SUBTYPE_BITS.get(subtype, 0)          # (float subtypes: float32 frames)
-                    limited = None
-                    if delivery.limiter is not None:
-                        # (None where the ceiling does not bind: the delivery then takes the route of one without a limiter)
-                        limited = _limited(dev, outs[slot], n, rate, delivery, bits, metered[slot])
-                    if limited is None:
-                        record, frames = delivery_gain(delivery, bits, metered[slot]), outs[slot]
-                    else:
-                        record, frames = limited
-                    deliveries.delivered[key] = record
-                    # queued behind the measurement; the array is valid after the one wait below
-                    try:
-                        deliveries.arrays[key] = dev.deliver(frames, n, 2, record.gain, bits, DITHERS[delivery.dither],
-                                                             delivery.seed, wait=False)
-                    finally:
-                        if limited is not None:
-                            frames.release() # (recycled by later work on this stream only, which is ordered behind the kernel)
-                    if loudness is not None:
-                        loudness("delivered:" + str(key), record)
+                # a delivery at another rate is cut from the rendering CONVERTED to that rate (mgx_convert_rate), measured
+                # at that rate: once per (rendering, rate), shared by every delivery that names the pair
+                converted, at_rate = {}, {}
+                try:
+                    for key, slot, subtype, delivery in deliveries.items:
+                        out_rate = delivery.rate(rate)
+                        if out_rate == rate:
+                            if slot not in metered:
+                                metered[slot] = dev.loudness(outs[slot], n, rate)
+                            source, length, reading = outs[slot], n, metered[slot]
+                        else:
+                            pair = (slot, out_rate)
+                            if pair not in converted:
+                                converted[pair] = dev.convert_rate(outs[slot], n, rate, out_rate)
+                                at_rate[pair] = dev.loudness(converted[pair].buf, converted[pair].frames, out_rate)
+                            source, length, reading = converted[pair].buf, converted[pair].frames, at_rate[pair]
+                        bits = SUBTYPE_BITS.get(subtype, 0)          # (float subtypes: float32 frames)
+                        limited = None
+                        if delivery.limiter is not None:
+                            # (None where the ceiling does not bind: the delivery then takes the route of one without a limiter)
+                            limited = _limited(dev, source, length, out_rate, delivery, bits, reading)
+                        if limited is None:
+                            record, frames = delivery_gain(delivery, bits, reading), source
+                        else:
+                            record, frames = limited
+                        record = replace(record, sample_rate=out_rate, frames=length, internal_rate=rate)
+                        deliveries.delivered[key] = record
+                        # queued behind the measurement; the array is valid after the one wait below
+                        try:
+                            deliveries.arrays[key] = dev.deliver(frames, length, 2, record.gain, bits, DITHERS[delivery.dither],
+                                                                 delivery.seed, wait=False)
+                        finally:
+                            if limited is not None:
+                                frames.release() # (recycled by later work on this stream only, which is ordered behind the kernel)
+                        if loudness is not None:
+                            loudness("delivered:" + str(key), record)
+                finally:
+                    for frames in converted.values():
+                        frames.release()         # (likewise: on every path, an exception's included)
             # queued one behind the other, then ONE wait; the arrays live in pinned host memory
             formats = encodings if encodings is not None else (None, None, None)
             pieces = []
