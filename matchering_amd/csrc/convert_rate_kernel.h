@@ -16,7 +16,8 @@
 // kernel loses more to its idle SIMDs than the wider reuse gains), else P = 1 where one period fits RESAMPLE_SPAN_MAX.
 // With P = 1 nothing is shared between periods, so a pair whose single period does not fit either (L >= 256 and M + W
 // frames too many) falls back to S = 256, k_resample's own tile: no pair mgx_resample accepts is refused here for its
-// span.
+// span.  What the host decides of a launch -- the arguments but the pointers, P, the grid and the LDS bytes -- is
+// convert_rate_launch, for mgx_convert_rate and tests/emu/emu_convert_rate.cpp alike.
 #pragma once
 
 #include "mgx_hd.h"
@@ -62,6 +63,24 @@ struct ConvertRateArgs {
     int S;                      // columns of a tile
     int hop;                    // (S / L) M: input frames between outputs t and t + S (used when P > 1 only)
 };
+
+// ---- what the host decides (mgx_convert_rate and the emulation alike) --------------------------------------------------
+struct ConvertRateLaunch {
+    int P;                      // the instantiation, as convert_rate_tiling gives it (0: `forced` does not fit, nothing is filled)
+    unsigned grid;              // tiles of P S outputs
+    size_t lds;                 // dynamic LDS: the tiling's span as float2 frames
+};
+// everything of the arguments but the pointers
+inline ConvertRateLaunch convert_rate_launch(ConvertRateArgs& a, const ResampleGeometry& g, long long n, long long n_out,
+                                             int forced = 0) {
+    const ConvertRateTiling t = convert_rate_tiling(g, forced);
+    if (t.P == 0) return {};
+    a.n = n, a.n_out = n_out;
+    a.L = g.L, a.M = g.M, a.W = g.W;
+    a.S = t.S, a.hop = t.S / g.L * g.M;
+    const long long tile = (long long)t.P * t.S;
+    return {t.P, (unsigned)((n_out + tile - 1) / tile), (size_t)t.span * sizeof(float2)};
+}
 
 // what is the same for every thread of a workgroup
 struct ConvertRateTile {

@@ -16,7 +16,9 @@
 // two words it needs from block q - 1 by a second call, nothing sequential, no neighbour -- loads it with one 16-byte
 // access and stores 8 bytes (16 bit), three words (24 bit, packed little-endian as k_pcm_encode packs them) or 16 bytes.
 // The samples % 4 behind the last quad go one each to the first threads of workgroup 0, as in k_pcm_encode's 24-bit path.
-// No LDS, no barrier, nobody waits for anybody.  The bodies are MGX_HD so that tests/emu/emu_deliver.cpp runs them.
+// No LDS, no barrier, nobody waits for anybody.  The bodies are MGX_HD so that tests/emu/emu_deliver.cpp runs them; what
+// the host decides of a launch -- the arguments but the pointers, and the grid -- is deliver_launch and deliver_grid,
+// for mgx_deliver and the emulation alike.
 #pragma once
 
 #include "mgx_hd.h"
@@ -36,9 +38,16 @@ struct DeliverArgs {
     void* out;
 };
 
+// ---- what the host decides (mgx_deliver and the emulation alike) -------------------------------------------------------
 MGX_HD long long deliver_grid(long long samples) {
     const long long blocks = (samples / 4 + DELIVER_THREADS - 1) / DELIVER_THREADS;
     return blocks < 1 ? 1 : (blocks > DELIVER_GRID_MAX ? DELIVER_GRID_MAX : blocks);
+}
+// everything of the arguments but the pointers
+inline void deliver_launch(DeliverArgs& a, long long samples, double gain, int bits, int dither, unsigned long long seed) {
+    a.samples = samples, a.gain = gain;
+    a.bits = bits, a.dither = dither;
+    a.key0 = (unsigned)seed, a.key1 = (unsigned)(seed >> 32);
 }
 
 struct alignas(16) DeliverWords4 { unsigned x, y, z, w; };

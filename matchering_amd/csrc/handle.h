@@ -329,6 +329,22 @@ static int ensure_ctrl(mgx_handle* h) {
     return 0;
 }
 
+// The weights of a rate pair on the device: mgx_resample and mgx_convert_rate share the cache, so whichever of the two
+// (`entry`) meets a pair first designs and uploads it, once for both.
+static int resample_dev(mgx_handle* h, const char* entry, int rate_in, int rate_out, mgx_handle::ResampleDev** out) {
+    mgx_handle::ResampleDev& dev = h->resample_plans[{rate_in, rate_out}];
+    if (!dev.matrix.p) {
+        dev.plan = resample_design(rate_in, rate_out);
+        if (!dev.plan) return fail(MGX_ERR_UNSUPPORTED, std::string(entry) + ": no plan for these rates");
+        dev.host = resample_device_matrix(*dev.plan);
+        MGX_TRY(ensure(h, dev.matrix, dev.host.size() * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(dev.matrix.p, dev.host.data(), dev.host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        ++h->resample_designs;
+    }
+    *out = &dev;
+    return 0;
+}
+
 // an environment switch: "1" turns it on
 static bool env_flag(const char* name) {
     const char* e = std::getenv(name);

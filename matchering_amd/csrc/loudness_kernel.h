@@ -12,7 +12,9 @@
 //           sub-block boundary its run may hold; the same frames give its true-peak and sample-peak candidates
 //   reduce  groups of 16 threads (256 frames: one boundary at most) are summed in thread order by one thread each,
 //           then the groups of every sub-block of the tile in group order: a fixed order, so two runs agree bit for bit
-// The phases are MGX_HD functions over a per-thread LoudThread, so that tests/emu/emu_loudness.cpp runs the same code.
+// The phases are MGX_HD functions over a per-thread LoudThread, so that tests/emu/emu_loudness.cpp runs the same code;
+// what the host decides of a launch -- the arguments but the pointers and the error slot -- is loudness_launch, for
+// mgx_loudness and the emulation alike (the grid is the geometry's `workgroups`, the LDS LOUD_LDS_BYTES).
 #pragma once
 
 #include "mgx_hd.h"
@@ -32,6 +34,14 @@ struct LoudnessArgs {
     int* error;                 // the handle's error words, or null
     int error_slot;
 };
+
+// ---- what the host decides (mgx_loudness and the emulation alike) ------------------------------------------------------
+// everything of the arguments but the pointers and the error slot
+inline void loudness_launch(LoudnessArgs& a, const LoudnessPlan& plan, const LoudnessGeometry& g, long long n) {
+    a.n = n, a.nsub = g.nsub;
+    for (int i = 0; i < 10; ++i) a.c[i] = plan.c[i];
+    a.S = g.S, a.own = g.own, a.warmup = g.warmup;
+}
 
 constexpr int LOUD_APRON = 8;                                               // >= LOUD_TP_AFTER, LOUD_TP_BEFORE
 // a tile in LDS: frame i of [first - APRON, first + TILE + APRON) at slot i + i / 16, so that the threads of a wave,

@@ -286,6 +286,15 @@ int mgx_convolve(mgx_handle* h, const float* x_dev, int64_t n, const double* fir
     return 0;
 }
 
+// out[r] = the sum of part[r][0 .. chunks), in chunk order (mgx_clipped_piece_sumsq, mgx_window_energy)
+static void sum_partials(const double* part, int64_t rows, int chunks, double* out) {
+    for (int64_t r = 0; r < rows; ++r) {
+        double s = 0.0;
+        for (int c = 0; c < chunks; ++c) s += part[(size_t)r * chunks + c];
+        out[r] = s;
+    }
+}
+
 int mgx_clipped_piece_sumsq(mgx_handle* h, const float* mid_dev, int64_t n, int64_t piece_size, int32_t divisions,
                             double gain, double* sumsq) {
     if (!h || !mid_dev || !sumsq) return fail(MGX_ERR_ARGUMENT, "null argument");
@@ -297,11 +306,7 @@ int mgx_clipped_piece_sumsq(mgx_handle* h, const float* mid_dev, int64_t n, int6
     std::vector<double> part((size_t)divisions * chunks);
     HIP_TRY(hipMemcpyAsync(part.data(), h->partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MGX_TRY(sync_main(h));
-    for (int d = 0; d < divisions; ++d) {
-        double s = 0.0;
-        for (int c = 0; c < chunks; ++c) s += part[(size_t)d * chunks + c];
-        sumsq[d] = s;
-    }
+    sum_partials(part.data(), divisions, chunks, sumsq);
     return 0;
 }
 
@@ -391,14 +396,8 @@ int mgx_peak_count(mgx_handle* h, const float* x_dev, int64_t samples, double* p
 int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_rate, mgx_loudness_report* report,
                  double* sub_energy, int64_t capacity, int64_t* count) {
     // everything that depends on the numbers alone is settled before the handle is touched
-    if (!report) return fail(MGX_ERR_ARGUMENT, "null argument");
-    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "loudness is metered at sample rates of 8000 Hz and above");
-    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
-    if (n > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_loudness: tracks of more than 500 million frames are not metered here");
-    const int S = (sample_rate + 5) / 10;
-    const int64_t nsub = n / S;
-    if (count) *count = nsub;
-    if (sub_energy && capacity < nsub) return fail(MGX_ERR_ARGUMENT, "the energy array holds fewer sub-blocks than the track has");
+    int S = 0;
+    MGX_TRY(loudness_request(report, n, sample_rate, sub_energy, capacity, count, &S));
     if (!h || (n > 0 && !x_dev)) return fail(MGX_ERR_ARGUMENT, "null argument");
     report->true_peak = report->sample_peak = 0.0;
     if (n == 0) {
@@ -418,14 +417,9 @@ int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_ra
     MGX_TRY(ensure(h, h->loudness_out, doubles * sizeof(double)));
     MGX_TRY(ensure_pinned(h, std::max(doubles * sizeof(double), (size_t)1 << 16)));
     LoudnessArgs a;
+    loudness_launch(a, dev.plan, g, n);
     a.x = x_dev;
-    a.n = n;
     a.table = (const double*)dev.table.p;
-    std::memcpy(a.c, dev.plan.c, sizeof a.c);
-    a.S = g.S;
-    a.own = g.own;
-    a.warmup = g.warmup;
-    a.nsub = g.nsub;
     a.e = (double*)h->loudness_out.p;
     a.peaks = a.e + (size_t)g.nsub * 2;
     a.error = h->error_dev;
@@ -471,12 +465,7 @@ int mgx_window_energy(mgx_handle* h, const float* x_dev, int64_t n, int64_t size
     HIP_TRY(hipMemcpyAsync(h->pinned, h->partial.p, bytes, hipMemcpyDeviceToHost, h->stream));
     MGX_TRY(sync_main(h));
     MGX_TRY(check_device_error(h));
-    const double* part = (const double*)h->pinned;
-    for (int64_t w = 0; w < windows; ++w) {
-        double s = 0.0;
-        for (int c = 0; c < chunks; ++c) s += part[(size_t)w * chunks + c];
-        energy[w] = s;
-    }
+    sum_partials((const double*)h->pinned, windows, chunks, energy);
     return 0;
 }
 
@@ -517,20 +506,13 @@ int mgx_pcm_encode(mgx_handle* h, const float* x_dev, int64_t samples, int32_t b
 int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain, int32_t bits, int32_t dither,
                 uint64_t seed, void* out_dev) {
     if (!h || !x_dev || !out_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
-    MGX_TRY(deliver_format_check(bits, dither));
-    if (samples < 0) return fail(MGX_ERR_ARGUMENT, "samples: negative");
-    if (!std::isfinite(gain)) return fail(MGX_ERR_ARGUMENT, "gain: not a finite number");
+    MGX_TRY(deliver_check(samples, gain, bits, dither));
     if ((((size_t)x_dev) | ((size_t)out_dev)) & 15) return fail(MGX_ERR_ARGUMENT, "x_dev / out_dev: must be 16-byte aligned");
     if (samples == 0) return 0;
     MGX_TRY(open_main(h));
     DeliverArgs a;
+    deliver_launch(a, samples, gain, bits, dither, seed);
     a.x = x_dev;
-    a.samples = samples;
-    a.gain = gain;
-    a.bits = bits;
-    a.dither = dither;
-    a.key0 = (unsigned)seed;
-    a.key1 = (unsigned)(seed >> 32);
     a.out = out_dev;
     hipLaunchKernelGGL(k_deliver, dim3((unsigned)deliver_grid(samples)), dim3(DELIVER_THREADS), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
@@ -540,14 +522,9 @@ int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain,
 int mgx_tp_limit(mgx_handle* h, const float* x_dev, int64_t n, double pre_gain, double ceiling, int32_t lookahead,
                  double release, float* out_dev, double* max_reduction) {
     // everything that depends on the numbers alone is settled before the handle is touched
-    if (n < 0) return fail(MGX_ERR_ARGUMENT, "n: negative");
-    if (!std::isfinite(pre_gain) || pre_gain <= 0.0) return fail(MGX_ERR_ARGUMENT, "pre_gain: must be finite and positive");
-    if (!std::isfinite(ceiling) || ceiling <= 0.0) return fail(MGX_ERR_ARGUMENT, "ceiling: must be finite and positive");
-    if (lookahead < 1 || lookahead > TPL_LOOKAHEAD_MAX)
-        return fail(MGX_ERR_ARGUMENT, "lookahead: outside [1, " + std::to_string(TPL_LOOKAHEAD_MAX) + "] frames");
-    if (!std::isfinite(release) || release < 0.0 || release > TPL_RELEASE_MAX)
-        return fail(MGX_ERR_ARGUMENT, "release: outside [0, 2^22] frames");
-    if (n > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_tp_limit: tracks of more than 500 million frames are not limited here");
+    static_assert(TPL_LOOKAHEAD_MAX == TP_LIMIT_LOOKAHEAD_MAX && TPL_RELEASE_MAX == TP_LIMIT_RELEASE_MAX,
+                  "tp_limit_check refuses what the kernels' LDS and decay tables do not hold");
+    MGX_TRY(tp_limit_check(n, pre_gain, ceiling, lookahead, release));
     if (!h) return fail(MGX_ERR_ARGUMENT, "null handle");
     if (!x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
     if (!out_dev) return fail(MGX_ERR_ARGUMENT, "out_dev: null");
@@ -591,48 +568,25 @@ int mgx_tp_limit(mgx_handle* h, const float* x_dev, int64_t n, double pre_gain, 
 int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels, int32_t rate_in, int32_t rate_out,
                  float* out_dev, int64_t out_capacity_frames, int64_t* n_out) {
     // everything that depends on the numbers alone is settled before the handle is touched
-    if (!n_out) return fail(MGX_ERR_ARGUMENT, "null argument");
-    if (channels != 1 && channels != 2) return fail(MGX_ERR_ARGUMENT, "a track to convert has one or two channels");
-    if (rate_in <= 0 || rate_out <= 0) return fail(MGX_ERR_ARGUMENT, "sample rates must be positive");
-    if (rate_in == rate_out) return fail(MGX_ERR_ARGUMENT, "the track is at the requested rate already");
-    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
     ResampleGeometry g;
-    std::string why;
-    if (resample_geometry(rate_in, rate_out, &g, &why) != 0)
-        return fail(MGX_ERR_UNSUPPORTED, "mgx_resample " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " Hz: " + why);
-    const int64_t frames = resample_length(n, rate_in, rate_out);
-    if (n > RESAMPLE_FRAMES_MAX || frames > RESAMPLE_FRAMES_MAX)
-        return fail(MGX_ERR_UNSUPPORTED, "mgx_resample: tracks of more than 500 million frames are not converted here");
-    *n_out = frames;
+    MGX_TRY(resample_request("mgx_resample", "the track is", &channels, n, rate_in, rate_out, &g, n_out));
     if (!out_dev) return 0;                                     // the caller asked for the length only
     if (!h || !x_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const int64_t frames = *n_out;
     if (out_capacity_frames < frames) return fail(MGX_ERR_ARGUMENT, "the output holds fewer frames than the conversion gives");
     if (frames == 0) return 0;
     MGX_TRY(open_main(h));
-    mgx_handle::ResampleDev& dev = h->resample_plans[{rate_in, rate_out}];
-    if (!dev.matrix.p) {
-        dev.plan = resample_design(rate_in, rate_out);
-        if (!dev.plan) return fail(MGX_ERR_UNSUPPORTED, "mgx_resample: no plan for these rates");
-        dev.host = resample_device_matrix(*dev.plan);
-        MGX_TRY(ensure(h, dev.matrix, dev.host.size() * sizeof(double)));
-        HIP_TRY(hipMemcpyAsync(dev.matrix.p, dev.host.data(), dev.host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        ++h->resample_designs;
-    }
+    mgx_handle::ResampleDev* dev = nullptr;
+    MGX_TRY(resample_dev(h, "mgx_resample", rate_in, rate_out, &dev));
     ResampleArgs a;
+    const ResampleLaunch launch = resample_launch(a, g, n, frames, channels);
     a.x = x_dev;
-    a.n = n;
-    a.w = (const double*)dev.matrix.p;
-    a.L = g.L;
-    a.M = g.M;
-    a.W = g.W;
+    a.w = (const double*)dev->matrix.p;
     a.out = out_dev;
-    a.n_out = frames;
-    const unsigned grid = (unsigned)((frames + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK);
-    const size_t lds = (size_t)g.span * channels * sizeof(float);
     if (channels == 2)
-        hipLaunchKernelGGL(k_resample<2>, dim3(grid), dim3(RESAMPLE_BLOCK), lds, h->stream, a);
+        hipLaunchKernelGGL(k_resample<2>, dim3(launch.grid), dim3(RESAMPLE_BLOCK), launch.lds, h->stream, a);
     else
-        hipLaunchKernelGGL(k_resample<1>, dim3(grid), dim3(RESAMPLE_BLOCK), lds, h->stream, a);
+        hipLaunchKernelGGL(k_resample<1>, dim3(launch.grid), dim3(RESAMPLE_BLOCK), launch.lds, h->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -640,53 +594,27 @@ int mgx_resample(mgx_handle* h, const float* x_dev, int64_t n, int32_t channels,
 int mgx_convert_rate(mgx_handle* h, const float* x_dev, int64_t n, int32_t rate_in, int32_t rate_out, float* out_dev,
                      int64_t out_capacity_frames, int64_t* n_out) {
     // everything that depends on the numbers alone is settled before the handle is touched (mgx_resample's contract)
-    if (!n_out) return fail(MGX_ERR_ARGUMENT, "null argument");
-    if (rate_in <= 0 || rate_out <= 0) return fail(MGX_ERR_ARGUMENT, "sample rates must be positive");
-    if (rate_in == rate_out) return fail(MGX_ERR_ARGUMENT, "the frames are at the requested rate already");
-    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
     ResampleGeometry g;
-    std::string why;
-    if (resample_geometry(rate_in, rate_out, &g, &why) != 0)
-        return fail(MGX_ERR_UNSUPPORTED, "mgx_convert_rate " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " Hz: " + why);
-    const int64_t frames = resample_length(n, rate_in, rate_out);
-    if (n > RESAMPLE_FRAMES_MAX || frames > RESAMPLE_FRAMES_MAX)
-        return fail(MGX_ERR_UNSUPPORTED, "mgx_convert_rate: tracks of more than 500 million frames are not converted here");
-    *n_out = frames;
+    MGX_TRY(resample_request("mgx_convert_rate", "the frames are", nullptr, n, rate_in, rate_out, &g, n_out));
     if (!out_dev) return 0;                                     // the caller asked for the length only
     if (!h || !x_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const int64_t frames = *n_out;
     if (out_capacity_frames < frames) return fail(MGX_ERR_ARGUMENT, "the output holds fewer frames than the conversion gives");
     if (frames == 0) return 0;
     MGX_TRY(open_main(h));
-    // (mgx_resample's cache: whichever of the two meets a rate pair first designs and uploads it, once for both)
-    mgx_handle::ResampleDev& dev = h->resample_plans[{rate_in, rate_out}];
-    if (!dev.matrix.p) {
-        dev.plan = resample_design(rate_in, rate_out);
-        if (!dev.plan) return fail(MGX_ERR_UNSUPPORTED, "mgx_convert_rate: no plan for these rates");
-        dev.host = resample_device_matrix(*dev.plan);
-        MGX_TRY(ensure(h, dev.matrix, dev.host.size() * sizeof(double)));
-        HIP_TRY(hipMemcpyAsync(dev.matrix.p, dev.host.data(), dev.host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        ++h->resample_designs;
-    }
-    const ConvertRateTiling tiling = convert_rate_tiling(g);
+    mgx_handle::ResampleDev* dev = nullptr;
+    MGX_TRY(resample_dev(h, "mgx_convert_rate", rate_in, rate_out, &dev));
     ConvertRateArgs a;
+    const ConvertRateLaunch launch = convert_rate_launch(a, g, n, frames);
     a.x = x_dev;
-    a.n = n;
-    a.w = (const double*)dev.matrix.p;
-    a.L = g.L;
-    a.M = g.M;
-    a.W = g.W;
+    a.w = (const double*)dev->matrix.p;
     a.out = out_dev;
-    a.n_out = frames;
-    a.S = tiling.S;
-    a.hop = tiling.S / g.L * g.M;
-    const long long tile = (long long)tiling.P * tiling.S;
-    const unsigned grid = (unsigned)((frames + tile - 1) / tile);
-    const size_t lds = (size_t)tiling.span * sizeof(float2);
-    switch (tiling.P) {
-        case 8: hipLaunchKernelGGL(k_convert_rate<8>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
-        case 4: hipLaunchKernelGGL(k_convert_rate<4>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
-        case 2: hipLaunchKernelGGL(k_convert_rate<2>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
-        default: hipLaunchKernelGGL(k_convert_rate<1>, dim3(grid), dim3(CONVERT_RATE_BLOCK), lds, h->stream, a); break;
+    const dim3 grid(launch.grid), block(CONVERT_RATE_BLOCK);
+    switch (launch.P) {
+        case 8: hipLaunchKernelGGL(k_convert_rate<8>, grid, block, launch.lds, h->stream, a); break;
+        case 4: hipLaunchKernelGGL(k_convert_rate<4>, grid, block, launch.lds, h->stream, a); break;
+        case 2: hipLaunchKernelGGL(k_convert_rate<2>, grid, block, launch.lds, h->stream, a); break;
+        default: hipLaunchKernelGGL(k_convert_rate<1>, grid, block, launch.lds, h->stream, a); break;
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -750,25 +678,12 @@ int mgx_master_with_profile(mgx_handle* h, const float* target_dev, int64_t n_ta
 int mgx_profile_merge(mgx_handle* h, const void* const* profiles_dev, const int32_t* weights, int32_t count,
                       const mgx_config* cfg, void* profile_dev) {
     if (!h || !profiles_dev || !cfg || !profile_dev) return fail(MGX_ERR_ARGUMENT, "null argument");
-    if (count < 1 || count > MGX_PROFILE_MERGE_MAX)
-        return fail(MGX_ERR_ARGUMENT, "mgx_profile_merge takes 1 to " + std::to_string(MGX_PROFILE_MERGE_MAX) + " profiles, got " +
-                                      std::to_string(count) + ": merge in groups, a merged profile is a source like any other");
-    size_t bytes = 0;
-    MGX_TRY(mgx_profile_bytes(cfg, &bytes));
+    MGX_TRY(profile_merge_check(profiles_dev, weights, count, cfg, profile_dev));
     ProfileMergeArgs a = {};
     a.count = count;
-    const uintptr_t out = (uintptr_t)profile_dev;
     for (int i = 0; i < count; ++i) {
-        const int32_t w = weights ? weights[i] : 1;
-        if (!profiles_dev[i]) return fail(MGX_ERR_ARGUMENT, "null profile at position " + std::to_string(i));
-        if (w < 1 || w > 65536)
-            return fail(MGX_ERR_ARGUMENT, "weight " + std::to_string(w) + " at position " + std::to_string(i) + " is outside [1, 65536]");
-        const uintptr_t src = (uintptr_t)profiles_dev[i];
-        if (src < out + bytes && out < src + bytes)
-            return fail(MGX_ERR_ARGUMENT, "profile_dev overlaps the source at position " + std::to_string(i) +
-                                          ": the merged profile needs a block of its own");
         a.src[i] = (const mgx_profile_header*)profiles_dev[i];
-        a.weight[i] = w;
+        a.weight[i] = weights ? weights[i] : 1;
     }
     MGX_TRY(open_main(h));
     const int bins = cfg->fft_size / 2 + 1;

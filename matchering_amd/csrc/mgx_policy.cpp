@@ -83,6 +83,76 @@ int deliver_format_check(int32_t bits, int32_t dither) {
     return 0;
 }
 
+int resample_request(const char* entry, const char* subject, const int32_t* channels, int64_t n, int32_t rate_in,
+                     int32_t rate_out, ResampleGeometry* g, int64_t* n_out) {
+    if (!n_out) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (channels && *channels != 1 && *channels != 2) return fail(MGX_ERR_ARGUMENT, "a track to convert has one or two channels");
+    if (rate_in <= 0 || rate_out <= 0) return fail(MGX_ERR_ARGUMENT, "sample rates must be positive");
+    if (rate_in == rate_out) return fail(MGX_ERR_ARGUMENT, std::string(subject) + " at the requested rate already");
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
+    std::string why;
+    if (resample_geometry(rate_in, rate_out, g, &why) != 0)
+        return fail(MGX_ERR_UNSUPPORTED, std::string(entry) + " " + std::to_string(rate_in) + " -> " + std::to_string(rate_out) + " Hz: " + why);
+    const int64_t frames = resample_length(n, rate_in, rate_out);
+    if (n > RESAMPLE_FRAMES_MAX || frames > RESAMPLE_FRAMES_MAX)
+        return fail(MGX_ERR_UNSUPPORTED, std::string(entry) + ": tracks of more than 500 million frames are not converted here");
+    *n_out = frames;
+    return 0;
+}
+
+int loudness_request(const mgx_loudness_report* report, int64_t n, int32_t sample_rate, const double* sub_energy,
+                     int64_t capacity, int64_t* count, int* S) {
+    if (!report) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "loudness is metered at sample rates of 8000 Hz and above");
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "negative frame count");
+    if (n > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_loudness: tracks of more than 500 million frames are not metered here");
+    *S = (sample_rate + 5) / 10;
+    const int64_t nsub = n / *S;
+    if (count) *count = nsub;
+    if (sub_energy && capacity < nsub) return fail(MGX_ERR_ARGUMENT, "the energy array holds fewer sub-blocks than the track has");
+    return 0;
+}
+
+int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither) {
+    MGX_TRY(deliver_format_check(bits, dither));
+    if (samples < 0) return fail(MGX_ERR_ARGUMENT, "samples: negative");
+    if (!std::isfinite(gain)) return fail(MGX_ERR_ARGUMENT, "gain: not a finite number");
+    return 0;
+}
+
+int tp_limit_check(int64_t n, double pre_gain, double ceiling, int32_t lookahead, double release) {
+    if (n < 0) return fail(MGX_ERR_ARGUMENT, "n: negative");
+    if (!std::isfinite(pre_gain) || pre_gain <= 0.0) return fail(MGX_ERR_ARGUMENT, "pre_gain: must be finite and positive");
+    if (!std::isfinite(ceiling) || ceiling <= 0.0) return fail(MGX_ERR_ARGUMENT, "ceiling: must be finite and positive");
+    if (lookahead < 1 || lookahead > TP_LIMIT_LOOKAHEAD_MAX)
+        return fail(MGX_ERR_ARGUMENT, "lookahead: outside [1, " + std::to_string(TP_LIMIT_LOOKAHEAD_MAX) + "] frames");
+    if (!std::isfinite(release) || release < 0.0 || release > TP_LIMIT_RELEASE_MAX)
+        return fail(MGX_ERR_ARGUMENT, "release: outside [0, 2^22] frames");
+    if (n > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_tp_limit: tracks of more than 500 million frames are not limited here");
+    return 0;
+}
+
+int profile_merge_check(const void* const* profiles_dev, const int32_t* weights, int32_t count, const mgx_config* cfg,
+                        const void* profile_dev) {
+    if (count < 1 || count > MGX_PROFILE_MERGE_MAX)
+        return fail(MGX_ERR_ARGUMENT, "mgx_profile_merge takes 1 to " + std::to_string(MGX_PROFILE_MERGE_MAX) + " profiles, got " +
+                                      std::to_string(count) + ": merge in groups, a merged profile is a source like any other");
+    size_t bytes = 0;
+    MGX_TRY(mgx_profile_bytes(cfg, &bytes));
+    const uintptr_t out = (uintptr_t)profile_dev;
+    for (int i = 0; i < count; ++i) {
+        const int32_t w = weights ? weights[i] : 1;
+        if (!profiles_dev[i]) return fail(MGX_ERR_ARGUMENT, "null profile at position " + std::to_string(i));
+        if (w < 1 || w > 65536)
+            return fail(MGX_ERR_ARGUMENT, "weight " + std::to_string(w) + " at position " + std::to_string(i) + " is outside [1, 65536]");
+        const uintptr_t src = (uintptr_t)profiles_dev[i];
+        if (src < out + bytes && out < src + bytes)
+            return fail(MGX_ERR_ARGUMENT, "profile_dev overlaps the source at position " + std::to_string(i) +
+                                          ": the merged profile needs a block of its own");
+    }
+    return 0;
+}
+
 // the numerator of g_peak: the linear ceiling less the quantiser's head-room (mgx_delivery_limit_step's ceiling is the same number)
 static int delivery_room(const mgx_delivery* delivery, double* room_out) {
     // A: the most the meter's interpolator makes of errors of magnitude 1 -- the largest per-phase sum of |taps|

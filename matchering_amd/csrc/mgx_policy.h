@@ -1,6 +1,7 @@
 // The part of libmgx.so that touches no device (mgx_policy.cpp): the calling thread's error text, the validation of a
-// Config, and the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
-// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_delivery_gain, mgx_delivery_limit_step, mgx_profile_bytes.
+// Config, the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
+// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_delivery_gain, mgx_delivery_limit_step, mgx_profile_bytes --
+// and what the device entry points settle from their numbers alone before they touch a handle.
 // No HIP here: g++ compiles the unit by itself (tests/emu/emu_policy_driver.cpp runs it under the sanitizers), and
 // mgx.hip uses what is declared below.
 #pragma once
@@ -11,6 +12,7 @@
 #include "../../include/mgx.h"
 #include "fir_design.h"
 #include "loudness_plan.h"
+#include "resample_plan.h"
 
 namespace mgx {
 
@@ -29,5 +31,22 @@ int check_length(long long n);
 FirDesignParams fir_design_params(const mgx_config& c);
 void loudness_fill(const LoudnessGated& g, int64_t nsub, int S, mgx_loudness_report* report);
 int deliver_format_check(int32_t bits, int32_t dither);
+
+// What the device entry points of mgx.hip settle from the numbers alone, before they look at their handle or their
+// pointers, each with the entry point's own codes and messages in its own order.  resample_request is mgx_resample's
+// (`channels` its argument) and mgx_convert_rate's (`channels` null: resident frames are stereo) up to the output length,
+// which goes to *n_out; `subject` is "the track is" / "the frames are".  loudness_request writes *count (where given)
+// and *S, the frames of a sub-block, once the frame count is accepted.
+int resample_request(const char* entry, const char* subject, const int32_t* channels, int64_t n, int32_t rate_in,
+                     int32_t rate_out, ResampleGeometry* g, int64_t* n_out);
+int loudness_request(const mgx_loudness_report* report, int64_t n, int32_t sample_rate, const double* sub_energy,
+                     int64_t capacity, int64_t* count, int* S);
+int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither);
+// (the ranges include/mgx.h documents; mgx.hip holds tp_limit_kernel.h's constants to them)
+constexpr int TP_LIMIT_LOOKAHEAD_MAX = 2048;
+constexpr double TP_LIMIT_RELEASE_MAX = 4194304.0;             // 2^22 frames
+int tp_limit_check(int64_t n, double pre_gain, double ceiling, int32_t lookahead, double release);
+int profile_merge_check(const void* const* profiles_dev, const int32_t* weights, int32_t count, const mgx_config* cfg,
+                        const void* profile_dev);
 
 }  // namespace mgx

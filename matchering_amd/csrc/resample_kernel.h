@@ -8,7 +8,9 @@
 // of tap row k, so a wave's load is 512 contiguous bytes, where a row-per-phase matrix would have every lane on a cache
 // line of its own.  Samples are promoted to float64, the sum runs in float64 with explicit fma in tap order, and the
 // store rounds once to float32: float32(host result) up to a flip of the last bit where the two orders of summation
-// straddle a rounding boundary.  A mono input is summed once and written to both columns (dsp.py:45-46).
+// straddle a rounding boundary.  A mono input is summed once and written to both columns (dsp.py:45-46).  What the host
+// decides of a launch -- the arguments but the pointers, the grid and the LDS bytes -- is resample_launch, for
+// mgx_resample and tests/emu/emu_resample.cpp alike.
 #pragma once
 
 #include <cstring>
@@ -26,6 +28,18 @@ struct ResampleArgs {
     float* out;                 // [n_out][2]
     long long n_out;
 };
+
+// ---- what the host decides (mgx_resample and the emulation alike) ------------------------------------------------------
+struct ResampleLaunch {
+    unsigned grid;              // workgroups of RESAMPLE_BLOCK outputs
+    size_t lds;                 // dynamic LDS: the longest span a workgroup stages, `channels` floats a frame
+};
+// everything of the arguments but the pointers
+inline ResampleLaunch resample_launch(ResampleArgs& a, const ResampleGeometry& g, long long n, long long n_out, int channels) {
+    a.n = n, a.n_out = n_out;
+    a.L = g.L, a.M = g.M, a.W = g.W;
+    return {(unsigned)((n_out + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK), (size_t)g.span * channels * sizeof(float)};
+}
 
 // what is the same for every thread of a workgroup
 struct ResampleTile {

@@ -1,9 +1,10 @@
 // CPU emulation of the deliveries' sample-rate converter -- TEST INFRASTRUCTURE (tests/test_convert_rate_host.py).
 //
-// Compiled by tests/emu/build_convert_rate.py with a plain host compiler and -DMGX_HOST_EMU: the host plan
-// (matchering_amd/csrc/resample_plan.cpp) as the library compiles it, the tiling rule and the SAME per-thread phase
-// functions k_convert_rate inlines (convert_rate_kernel.h), driven by a loop over thread ids where the GPU has a
-// workgroup and a plain sequence point where it has a barrier.  Not part of the product.
+// Compiled by tests/emu/build.py ("convert_rate") with a plain host compiler and -DMGX_HOST_EMU: the host plan
+// (matchering_amd/csrc/resample_plan.cpp) as the library compiles it, the tiling rule, the launch as mgx_convert_rate
+// fills it (convert_rate_launch) and the SAME per-thread phase functions k_convert_rate inlines
+// (convert_rate_kernel.h), driven by a loop over thread ids where the GPU has a workgroup and a plain sequence point
+// where it has a barrier.  Not part of the product.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -20,6 +21,18 @@ extern "C" int emu_convert_rate_tiling(int rate_in, int rate_out, int forced, in
     if (resample_geometry(rate_in, rate_out, &g, &why) != 0) return -1;
     const ConvertRateTiling t = convert_rate_tiling(g, forced);
     tiling[0] = t.P, tiling[1] = t.S, tiling[2] = t.span;
+    return 0;
+}
+
+// launch[0..2] = P, the grid and the dynamic LDS bytes mgx_convert_rate launches with for n_out outputs (`forced` as
+// above; P = 0: nothing else is set); -1 for a refused rate pair
+extern "C" int emu_convert_rate_launch(int rate_in, int rate_out, int forced, long long n_out, long long* launch) {
+    ResampleGeometry g;
+    std::string why;
+    if (resample_geometry(rate_in, rate_out, &g, &why) != 0) return -1;
+    ConvertRateArgs a;
+    const ConvertRateLaunch l = convert_rate_launch(a, g, 0, n_out, forced);
+    launch[0] = l.P, launch[1] = l.grid, launch[2] = (long long)l.lds;
     return 0;
 }
 
@@ -57,28 +70,22 @@ extern "C" long long emu_convert_rate(const float* x, long long n, long long x_f
                                       long long first_tile, double* sums, float* out) {
     const auto plan = resample_design(rate_in, rate_out);
     if (!plan) return -1;
-    const ConvertRateTiling tiling = convert_rate_tiling(plan->g, forced);
-    if (tiling.P == 0) return -2;
-    const std::vector<double> matrix = resample_device_matrix(*plan);
-    const long long out_first = first_tile * tiling.P * tiling.S;
     ConvertRateArgs a;
+    const ConvertRateLaunch launch = convert_rate_launch(a, plan->g, n, resample_length(n, rate_in, rate_out), forced);
+    if (launch.P == 0) return -2;
+    const std::vector<double> matrix = resample_device_matrix(*plan);
+    const long long out_first = first_tile * launch.P * a.S;
     a.x = x - 2 * x_first;
-    a.n = n;
     a.w = matrix.data();
-    a.L = plan->g.L;
-    a.M = plan->g.M;
-    a.W = plan->g.W;
     a.out = out - 2 * out_first;
-    a.n_out = resample_length(n, rate_in, rate_out);
-    a.S = tiling.S;
-    a.hop = tiling.S / plan->g.L * plan->g.M;
     double* all = sums - 2 * out_first;
+    const int span_max = (int)(launch.lds / sizeof(float2));        // frames the launch's LDS holds
     try {
-        switch (tiling.P) {
-            case 8: run<8>(a, tiling.span, first_tile, x_first, all); break;
-            case 4: run<4>(a, tiling.span, first_tile, x_first, all); break;
-            case 2: run<2>(a, tiling.span, first_tile, x_first, all); break;
-            default: run<1>(a, tiling.span, first_tile, x_first, all); break;
+        switch (launch.P) {
+            case 8: run<8>(a, span_max, first_tile, x_first, all); break;
+            case 4: run<4>(a, span_max, first_tile, x_first, all); break;
+            case 2: run<2>(a, span_max, first_tile, x_first, all); break;
+            default: run<1>(a, span_max, first_tile, x_first, all); break;
         }
     } catch (int code) {
         return -code;

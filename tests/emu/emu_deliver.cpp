@@ -1,8 +1,8 @@
 // CPU emulation of the delivery kernel -- TEST INFRASTRUCTURE (tests/test_delivery_host.py).
 //
-// Compiled by tests/emu/build_deliver.py with a plain host compiler and -DMGX_HOST_EMU: the SAME per-thread body
-// k_deliver inlines (matchering_amd/csrc/deliver_kernel.h), driven by a loop over workgroups and thread ids.  Not part of
-// the product.
+// Compiled by tests/emu/build.py ("deliver") with a plain host compiler and -DMGX_HOST_EMU: the launch as mgx_deliver
+// fills it (deliver_launch, deliver_grid) and the SAME per-thread body k_deliver inlines
+// (matchering_amd/csrc/deliver_kernel.h), driven by a loop over workgroups and thread ids.  Not part of the product.
 #include "../../matchering_amd/csrc/deliver_kernel.h"
 
 using namespace mgx;
@@ -19,13 +19,8 @@ extern "C" long long emu_deliver_grid(long long samples) { return deliver_grid(s
 extern "C" long long emu_deliver(const float* x, long long samples, double gain, int bits, int dither,
                                  unsigned long long seed, void* out, long long grid) {
     DeliverArgs a;
+    deliver_launch(a, samples, gain, bits, dither, seed);
     a.x = x;
-    a.samples = samples;
-    a.gain = gain;
-    a.bits = bits;
-    a.dither = dither;
-    a.key0 = (unsigned)seed;
-    a.key1 = (unsigned)(seed >> 32);
     a.out = out;
     if (grid <= 0) grid = deliver_grid(samples);
     for (long long b = 0; b < grid; ++b)
@@ -34,7 +29,7 @@ extern "C" long long emu_deliver(const float* x, long long samples, double gain,
 }
 
 #ifdef EMU_DELIVER_MAIN
-// A stand-alone run of the emulation (for a sanitizer build: g++ -fsanitize=address,undefined -DEMU_DELIVER_MAIN):
+// A stand-alone run of the emulation under the sanitizers (tests/test_emu_drivers_host.py; build.py build_driver):
 // every width and dither at a few ragged sizes, exactly sized buffers.
 #include <cstdio>
 #include <cstdlib>

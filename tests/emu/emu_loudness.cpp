@@ -1,9 +1,10 @@
 // CPU emulation of the loudness meter -- TEST INFRASTRUCTURE (tests/test_loudness_host.py).
 //
-// Compiled by tests/emu/build_loudness.py with a plain host compiler and -DMGX_HOST_EMU: the host plan
-// (matchering_amd/csrc/loudness_plan.cpp) as the library compiles it, and the SAME per-thread phase functions
-// k_loudness inlines (loudness_kernel.h), driven by a loop over thread ids where the GPU has a workgroup and a plain
-// sequence point where it has a barrier.  Not part of the product.
+// Compiled by tests/emu/build.py ("loudness") with a plain host compiler and -DMGX_HOST_EMU: the host plan
+// (matchering_amd/csrc/loudness_plan.cpp) as the library compiles it, the launch as mgx_loudness fills it
+// (loudness_launch) and the SAME per-thread phase functions k_loudness inlines (loudness_kernel.h), driven by a loop
+// over thread ids where the GPU has a workgroup and a plain sequence point where it has a barrier.  Not part of the
+// product.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -53,14 +54,9 @@ extern "C" long long emu_loudness(const float* x, long long n, int rate, double*
     const LoudnessPlan plan = loudness_design(rate);
     const LoudnessGeometry g = loudness_geometry(plan, n);
     LoudnessArgs a;
+    loudness_launch(a, plan, g, n);
     a.x = x;
-    a.n = n;
     a.table = plan.table.data();
-    std::memcpy(a.c, plan.c, sizeof a.c);
-    a.S = g.S;
-    a.own = g.own;
-    a.warmup = g.warmup;
-    a.nsub = g.nsub;
     a.e = e;
     a.peaks = peaks;
     a.error = error;

@@ -1,5 +1,5 @@
 // csrc/mgx_policy.cpp -- the entry points of libmgx.so that touch no device -- in a program of its own, for sanitizer
-// builds (tests/test_policy_host.py; tests/emu/build.py build_policy_driver).  It walks the edges the Python tests
+// builds (tests/test_policy_host.py; tests/emu/build.py, unit "policy").  It walks the edges the Python tests
 // name, states the value it expects at each, prints one line per group and exits non-zero when any differs.
 #include <cmath>
 #include <cstdio>
@@ -300,6 +300,122 @@ static void design_fir_sizes() {
     }
 }
 
+// ---- resample_request: what mgx_resample and mgx_convert_rate settle before they look at their handle ----------------
+static bool unsupported(int rc, const char* fragment) { return rc == MGX_ERR_UNSUPPORTED && std::strstr(mgx_last_error(), fragment); }
+
+static void resample_request_bounds() {
+    ResampleGeometry g;
+    int64_t n_out = -7;
+    auto track = [&](int32_t channels, int64_t n, int32_t in, int32_t out) {
+        return resample_request("mgx_resample", "the track is", &channels, n, in, out, &g, &n_out);
+    };
+    auto frames = [&](int64_t n, int32_t in, int32_t out) {
+        return resample_request("mgx_convert_rate", "the frames are", nullptr, n, in, out, &g, &n_out);
+    };
+    EXPECT(refused(resample_request("mgx_resample", "the track is", nullptr, 1000, 48000, 44100, &g, nullptr), "null argument"));
+    // channels: one or two, and no argument of mgx_convert_rate
+    EXPECT(refused(track(0, 1000, 48000, 44100), "one or two channels") && refused(track(3, 1000, 48000, 44100), "one or two channels"));
+    EXPECT(track(1, 1000, 48000, 44100) == 0 && n_out == 918 && track(2, 1000, 48000, 44100) == 0 && n_out == 918);
+    EXPECT(g.L == 147 && g.M == 160 && g.W == 140);
+    // the channels are looked at first, then the rates, then the frame count
+    n_out = -7;
+    EXPECT(refused(track(3, -1, 0, 0), "one or two channels") && refused(track(2, -1, 0, 0), "must be positive"));
+    EXPECT(refused(track(2, -1, 44100, 44100), "the track is at the requested rate already"));
+    EXPECT(refused(frames(-1, 44100, 44100), "the frames are at the requested rate already"));
+    // rates: positive
+    EXPECT(refused(frames(1000, 0, 44100), "must be positive") && refused(frames(1000, 48000, 0), "must be positive"));
+    EXPECT(refused(frames(1000, -48000, 44100), "must be positive") && refused(frames(1000, 48000, -1), "must be positive"));
+    EXPECT(n_out == -7);                                            // nothing reported so far
+    EXPECT(frames(1000, 1, 2) == 0 && n_out == 2000 && frames(1000, 2, 1) == 0 && n_out == 500);
+    // the frame count: not negative
+    EXPECT(refused(frames(-1, 48000, 44100), "negative frame count"));
+    EXPECT(frames(0, 48000, 44100) == 0 && n_out == 0 && frames(1, 48000, 44100) == 0 && n_out == 0 && frames(2, 48000, 44100) == 0 && n_out == 1);
+    // the plan's refusals name the entry and both rates: 4096 phases are the last accepted
+    n_out = -7;
+    EXPECT(unsupported(frames(1000, 4096, 4097), "mgx_convert_rate 4096 -> 4097 Hz: ") && std::strstr(mgx_last_error(), "more than 4096 phases"));
+    EXPECT(unsupported(track(2, 1000, 4096, 4097), "mgx_resample 4096 -> 4097 Hz: ") && n_out == -7);
+    EXPECT(frames(1000, 4097, 4096) == 0 && n_out == 999 && g.L == 4096 && g.M == 4097);
+    // 500 million frames, in and out
+    n_out = -7;
+    EXPECT(frames(500000000, 48000, 44100) == 0 && n_out == 459375000);
+    EXPECT(unsupported(frames(500000001, 48000, 44100), "mgx_convert_rate: tracks of more than 500 million frames"));
+    EXPECT(frames(250000000, 1, 2) == 0 && n_out == 500000000);
+    EXPECT(unsupported(track(1, 250000001, 1, 2), "mgx_resample: tracks of more than 500 million frames") && n_out == 500000000);
+}
+
+// ---- the ranges mgx_tp_limit, mgx_loudness, mgx_deliver and mgx_profile_merge check before their handle -----------------
+static void stage_checks() {
+    // mgx_tp_limit(n, pre_gain, ceiling, lookahead, release)
+    const double big = 1.7976931348623157e308, tiny = 5e-324, above = std::nextafter(TP_LIMIT_RELEASE_MAX, INFINITY);
+    const auto tp = tp_limit_check;
+    EXPECT(tp(0, tiny, tiny, 1, 0.0) == 0 && tp(500000000, big, big, 2048, 4194304.0) == 0);
+    EXPECT(refused(tp(-1, 0.0, 0.0, 0, -1.0), "n: negative"));
+    EXPECT(refused(tp(1, 0.0, 0.5, 1, 0.0), "pre_gain") && refused(tp(1, INFINITY, 0.5, 1, 0.0), "pre_gain") && refused(tp(1, NAN, 0.5, 1, 0.0), "pre_gain"));
+    EXPECT(refused(tp(1, 1.0, 0.0, 1, 0.0), "ceiling") && refused(tp(1, 1.0, INFINITY, 1, 0.0), "ceiling") && refused(tp(1, 1.0, NAN, 1, 0.0), "ceiling"));
+    EXPECT(refused(tp(1, 1.0, 0.5, 0, 0.0), "lookahead: outside [1, 2048]") && refused(tp(1, 1.0, 0.5, 2049, 0.0), "lookahead: outside [1, 2048]"));
+    EXPECT(refused(tp(1, 1.0, 0.5, 1, -tiny), "release: outside [0, 2^22]") && refused(tp(1, 1.0, 0.5, 1, above), "release: outside [0, 2^22]") &&
+           refused(tp(1, 1.0, 0.5, 1, NAN), "release"));
+    // (the length is looked at last, and is "not implemented", not a bad argument)
+    EXPECT(unsupported(tp(500000001, 1.0, 0.5, 1, 0.0), "mgx_tp_limit: tracks of more than 500 million frames") &&
+           refused(tp(500000001, 1.0, 0.5, 1, -1.0), "release"));
+
+    // mgx_loudness(report, n, sample_rate, sub_energy, capacity, count) -> S
+    mgx_loudness_report report;
+    const double somewhere = 0.0;
+    int64_t count = -7;
+    int S = -7;
+    auto loud = [&](int64_t n, int rate, const double* e = nullptr, int64_t capacity = 0) {
+        return loudness_request(&report, n, rate, e, capacity, &count, &S);
+    };
+    EXPECT(refused(loudness_request(nullptr, 10, 44100, nullptr, 0, &count, &S), "null argument") && refused(loud(10, 7999), "8000 Hz") &&
+           refused(loud(-1, 44100), "negative frame count") && count == -7 && S == -7);
+    EXPECT(loud(10, 8000) == 0 && S == 800 && count == 0 && loudness_request(&report, 0, 44100, nullptr, 0, nullptr, &S) == 0 && S == 4410);
+    EXPECT(loud(4409, 44100) == 0 && count == 0 && loud(4410, 44100) == 0 && count == 1);
+    EXPECT(loud(44100, 44104) == 0 && S == 4410 && loud(44100, 44105) == 0 && S == 4411 && count == 9);
+    EXPECT(loud(500000000, 44100) == 0 && count == 113378);
+    EXPECT(unsupported(loud(500000001, 44100), "mgx_loudness: tracks of more than 500 million frames") && count == 113378);
+    // an energy array that is too short is refused once the count has been reported; without an array no capacity is asked
+    EXPECT(refused(loud(44100, 44100, &somewhere, 9), "fewer sub-blocks") && count == 10);
+    EXPECT(loud(44100, 44100, &somewhere, 10) == 0 && loud(44100, 44100, nullptr, -1) == 0);
+
+    // mgx_deliver(samples, gain, bits, dither): the format first
+    EXPECT(deliver_check(0, 1.0, 16, 1) == 0 && deliver_check(1, -big, 0, 0) == 0 && deliver_check(7, 0.0, 32, 0) == 0);
+    EXPECT(refused(deliver_check(-1, 1.0, 24, 2), "samples: negative") && refused(deliver_check(-1, NAN, 20, 0), "bits"));
+    EXPECT(refused(deliver_check(-1, NAN, 16, 3), "dither") && refused(deliver_check(-1, NAN, 32, 1), "dither") && refused(deliver_check(-1, NAN, 16, 0), "samples"));
+    EXPECT(refused(deliver_check(4, INFINITY, 16, 0), "gain: not a finite number") && refused(deliver_check(4, -INFINITY, 16, 0), "gain") &&
+           refused(deliver_check(4, NAN, 16, 0), "gain"));
+
+    // mgx_profile_merge(profiles, weights, count, cfg, profile): blocks of `bytes` inside one arena, never read
+    mgx_config c;
+    mgx_config_default(&c);
+    size_t bytes = 0;
+    EXPECT(mgx_profile_bytes(&c, &bytes) == 0 && bytes > 0);
+    std::vector<char> arena(3 * bytes);
+    const char* base = arena.data();
+    // (arrays of exactly `count` entries: a read past them is the sanitizer's to find)
+    auto merge = [&](const std::vector<const void*>& src, const std::vector<int32_t>& w, const char* out, const mgx_config* cfg = nullptr) {
+        return profile_merge_check(src.data(), w.empty() ? nullptr : w.data(), (int32_t)src.size(), cfg ? cfg : &c, out);
+    };
+    const std::vector<const void*> one{base}, behind{base + bytes};
+    EXPECT(refused(merge({}, {}, base + bytes), "takes 1 to 64 profiles, got 0"));
+    EXPECT(merge(one, {}, base + bytes) == 0 && merge(one, {1}, base + bytes) == 0 && merge(one, {65536}, base + bytes) == 0);
+    EXPECT(refused(merge(one, {0}, base + bytes), "weight 0 at position 0") && refused(merge(one, {65537}, base + bytes), "weight 65537 at position 0"));
+    // the merged profile's block may touch a source's, not overlap it -- from either side
+    EXPECT(refused(merge(one, {}, base + bytes - 1), "overlaps the source at position 0") && refused(merge(one, {}, base), "overlaps the source at position 0"));
+    EXPECT(merge(behind, {}, base) == 0 && refused(merge(behind, {}, base + 1), "overlaps the source at position 0"));
+    mgx_config bad = c;
+    bad.fft_size = 4095;
+    EXPECT(refused(merge(one, {}, base + bytes, &bad), "[8, 65536]"));
+    std::vector<const void*> most(MGX_PROFILE_MERGE_MAX, base);
+    std::vector<int32_t> weights(MGX_PROFILE_MERGE_MAX, 3);
+    EXPECT(merge(most, weights, base + 2 * bytes) == 0);
+    EXPECT(refused(merge(std::vector<const void*>(MGX_PROFILE_MERGE_MAX + 1, base), {}, base + 2 * bytes), "got 65"));
+    most.back() = nullptr, weights.back() = 0;                  // (the null source is met before its weight)
+    EXPECT(refused(merge(most, weights, base + 2 * bytes), "null profile at position 63"));
+    most.back() = base + bytes + 1;
+    EXPECT(refused(merge(most, {}, base + 2 * bytes), "overlaps the source at position 63"));
+}
+
 int main() {
     int wrong = 0;
     config_bounds();
@@ -312,5 +428,9 @@ int main() {
     wrong += group_done("mgx_loudness_gate");
     design_fir_sizes();
     wrong += group_done("mgx_design_fir");
+    resample_request_bounds();
+    wrong += group_done("resample_request");
+    stage_checks();
+    wrong += group_done("stage_checks");
     return wrong ? 1 : 0;
 }

@@ -1,9 +1,10 @@
 // CPU emulation of the sample-rate converter -- TEST INFRASTRUCTURE (tests/test_resample_plan.py).
 //
-// Compiled by tests/emu/build_resample.py with a plain host compiler and -DMGX_HOST_EMU: the host plan
-// (matchering_amd/csrc/resample_plan.cpp) as the library compiles it, and the SAME per-thread phase functions
-// k_resample inlines (resample_kernel.h), driven by a loop over thread ids where the GPU has a workgroup and a plain
-// sequence point where it has a barrier.  Not part of the product.
+// Compiled by tests/emu/build.py ("resample") with a plain host compiler and -DMGX_HOST_EMU: the host plan
+// (matchering_amd/csrc/resample_plan.cpp) as the library compiles it, the launch as mgx_resample fills it
+// (resample_launch) and the SAME per-thread phase functions k_resample inlines (resample_kernel.h), driven by a loop
+// over thread ids where the GPU has a workgroup and a plain sequence point where it has a barrier.  Not part of the
+// product.
 #include <cstring>
 #include <vector>
 
@@ -32,6 +33,17 @@ extern "C" int emu_resample_rows(int rate_in, int rate_out, double* rows, double
     if (!plan) return -1;
     std::memcpy(rows, plan->rows.data(), plan->rows.size() * sizeof(double));
     *max_row_sum = plan->max_row_sum;
+    return 0;
+}
+
+// launch[0..1] = the grid and the dynamic LDS bytes mgx_resample launches with for n_out outputs; -1 for a refused rate pair
+extern "C" int emu_resample_launch(int rate_in, int rate_out, int channels, long long n_out, long long* launch) {
+    ResampleGeometry g;
+    std::string why;
+    if (resample_geometry(rate_in, rate_out, &g, &why) != 0) return -1;
+    ResampleArgs a;
+    const ResampleLaunch l = resample_launch(a, g, 0, n_out, channels);
+    launch[0] = l.grid, launch[1] = (long long)l.lds;
     return 0;
 }
 
@@ -64,19 +76,16 @@ extern "C" long long emu_resample(const float* x, long long n, int channels, int
     if (!plan) return -1;
     const std::vector<double> matrix = resample_device_matrix(*plan);
     ResampleArgs a;
+    const ResampleLaunch launch = resample_launch(a, plan->g, n, resample_length(n, rate_in, rate_out), channels);
     a.x = x;
-    a.n = n;
     a.w = matrix.data();
-    a.L = plan->g.L;
-    a.M = plan->g.M;
-    a.W = plan->g.W;
     a.out = out;
-    a.n_out = resample_length(n, rate_in, rate_out);
+    const int span_max = (int)(launch.lds / (channels * sizeof(float)));        // frames the launch's LDS holds
     try {
         if (channels == 2)
-            run<2>(a, plan->g.span, sums);
+            run<2>(a, span_max, sums);
         else
-            run<1>(a, plan->g.span, sums);
+            run<1>(a, span_max, sums);
     } catch (int) {
         return -2;
     }

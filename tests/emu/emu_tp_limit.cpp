@@ -1,6 +1,6 @@
 // CPU emulation of the deliveries' true-peak limiter -- TEST INFRASTRUCTURE (tests/test_tp_limiter_host.py).
 //
-// Compiled by tests/emu/build_tp_limit.py with a plain host compiler and -DMGX_HOST_EMU: the SAME per-thread phase
+// Compiled by tests/emu/build.py ("tp_limit") with a plain host compiler and -DMGX_HOST_EMU: the SAME per-thread phase
 // functions k_tp_envelope, k_tp_aggregate and k_tp_apply inline (matchering_amd/csrc/tp_limit_kernel.h) and the same
 // host plan, driven by a loop over thread ids where the GPU has a workgroup, a plain sequence point where it has a
 // barrier and one loop after the other where it has three launches.  Not part of the product.
@@ -98,7 +98,7 @@ extern "C" double emu_tp_limit(const float* x, long long n, double pre_gain, dou
 }
 
 #ifdef EMU_TP_LIMIT_MAIN
-// A stand-alone run of the emulation (for a sanitizer build: g++ -fsanitize=address,undefined -DEMU_TP_LIMIT_MAIN):
+// A stand-alone run of the emulation under the sanitizers (tests/test_emu_drivers_host.py; build.py build_driver):
 // exactly sized buffers at the sizes around a tile and the extreme look-aheads.
 #include <cstdio>
 int main() {

@@ -358,16 +358,9 @@ def limiter_configs(name):
 
 def load_emulation():
     """tests/emu/libmgx_emu.so (built when stale): the kernels' phase functions and the host's launch parameters."""
-    import ctypes
-    import importlib.util
-    import os
+    import emu_build
 
-    from conftest import ROOT
-
-    spec = importlib.util.spec_from_file_location("mgx_emu_build", os.path.join(ROOT, "tests", "emu", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return ctypes.CDLL(mod.build())
+    return emu_build.load()
 
 
 def limiter_geometry(emu, cfg):

@@ -9,27 +9,17 @@ wait" edges (or by a host synchronisation in between).
 """
 
 import ctypes
-import importlib.util
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-
-def _build_module():
-    spec = importlib.util.spec_from_file_location("mgx_emu_call_pipeline_build",
-                                                  os.path.join(ROOT, "tests", "emu", "build_call_pipeline.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+import emu_build
 
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = ctypes.CDLL(_build_module().build())
+    lib = emu_build.load("call_pipeline")
     lib.emu_pipeline_create.restype = ctypes.c_void_p
     lib.emu_pipeline_create.argtypes = []
     for name in ("destroy", "other_work", "drained"):
@@ -357,7 +347,7 @@ def test_standalone_driver_under_sanitizers(tmp_path):
     """The same unit in a program of its own, built with AddressSanitizer and UBSan, run once (nothing loaded into
     Python runs under a sanitizer)."""
     out = str(tmp_path / "driver")
-    _build_module().build_driver(out, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    emu_build.build_driver("call_pipeline", out, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
     done = subprocess.run([out], capture_output=True, text=True, timeout=60)
     assert done.returncode == 0, done.stdout + done.stderr
     assert "round 1:" in done.stdout

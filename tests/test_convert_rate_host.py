@@ -5,13 +5,12 @@ tests/test_resample_plan.py holds to ``resample.resample``), the tiling rule, ti
 """
 
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import emu_build
 from matchering_amd import _native
 from matchering_amd import resample as host
 
@@ -29,16 +28,10 @@ SPAN_MAX = 7680                     # RESAMPLE_SPAN_MAX: what a launch's LDS hol
 SPAN_SHARED = 5120                  # CONVERT_RATE_SPAN_MAX: what the rule lets a tile of P > 1 stage (four workgroups on a CU)
 
 
-def _load(script, module):
-    spec = importlib.util.spec_from_file_location(module, os.path.join(ROOT, "tests", "emu", script))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return ctypes.CDLL(mod.build())
-
-
 @pytest.fixture(scope="module")
 def emu():
-    lib = _load("build_convert_rate.py", "mgx_emu_convert_rate_build")
+    lib = emu_build.load("convert_rate")
+    lib.emu_convert_rate_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p]
     lib.emu_convert_rate.restype = ctypes.c_longlong
     lib.emu_convert_rate.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]
@@ -47,7 +40,7 @@ def emu():
 
 @pytest.fixture(scope="module")
 def old():
-    lib = _load("build_resample.py", "mgx_emu_resample_build")
+    lib = emu_build.load("resample")
     lib.emu_resample.restype = ctypes.c_longlong
     lib.emu_resample.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_void_p, ctypes.c_void_p]
@@ -120,6 +113,28 @@ def test_the_tiling_rule_gives_the_table(emu, old):
     assert tiling(emu, 192000, 44100, 8)[0] == 0 and tiling(emu, 192000, 44100, 4) == (4, 294, 5682)
     assert tiling(emu, 96000, 44100, 8) == (8, 294, 5400)
     assert tiling(emu, 44100, 8000, 4)[0] == 0 and tiling(emu, 44100, 8000, 1)[0] == 1
+
+
+@pytest.mark.parametrize("sr,new", PAIRS)
+def test_the_launch_is_the_tilings(emu, sr, new):
+    """What ``convert_rate_launch`` gives ``mgx_convert_rate`` and the emulation alike, for the rule's P and every
+    forced one that fits: the tiling's P, LDS for its span as float2 frames, within what a launch may ask for
+    (RESAMPLE_SPAN_MAX frames), and a workgroup per tile of P S outputs."""
+    launch = (ctypes.c_longlong * 3)()
+    for forced in (0, 1, 2, 4, 8):
+        P, S, span = tiling(emu, sr, new, forced)
+        if not P:
+            assert emu.emu_convert_rate_launch(sr, new, forced, 1, launch) == 0 and launch[0] == 0
+            continue
+        tile = P * S
+        for n_out in (1, tile - 1, tile, tile + 1):
+            assert emu.emu_convert_rate_launch(sr, new, forced, n_out, launch) == 0
+            got_P, grid, lds = launch
+            assert got_P == P
+            assert lds == span * 8
+            assert lds <= SPAN_MAX * 8
+            assert grid == -(-n_out // tile), (forced, n_out, grid)
+    assert emu.emu_convert_rate_launch(*REFUSED, 0, 1, launch) == -1
 
 
 def test_p_1_is_always_reachable(emu, old):

@@ -6,7 +6,6 @@ oracle, and the Python plumbing: ``Delivery`` / ``Result`` validation, batch job
 """
 
 import ctypes
-import importlib.util
 import json
 import math
 import os
@@ -15,9 +14,9 @@ import numpy as np
 import pytest
 
 import delivery_oracle as oracle
+import emu_build
 import loudness_oracle
 import matchering_amd as mg
-from conftest import ROOT
 from matchering_amd import _native, audio_io
 from matchering_amd.delivery import Delivered, Delivery, DeliveryRequest, delivery_gain
 from matchering_amd.loudness import Loudness
@@ -29,10 +28,7 @@ GRID_MAX = 2048                                                                 
 
 @pytest.fixture(scope="module")
 def emu():
-    spec = importlib.util.spec_from_file_location("mgx_emu_deliver_build", os.path.join(ROOT, "tests", "emu", "build_deliver.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    lib = ctypes.CDLL(mod.build())
+    lib = emu_build.load("deliver")
     lib.emu_philox.argtypes = [P, P, P]
     lib.emu_deliver_grid.restype = ctypes.c_longlong
     lib.emu_deliver_grid.argtypes = [ctypes.c_longlong]

@@ -6,12 +6,12 @@ library (libmgx.so) contains no host implementation of any kernel.
 """
 
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
+import emu_build
 import mastering_oracle as mo
 from cases import CASES, build_inputs, oracle_params
 from conftest import ROOT, rms_error
@@ -22,10 +22,7 @@ c_double_p = ctypes.POINTER(ctypes.c_double)
 
 @pytest.fixture(scope="module")
 def emu():
-    spec = importlib.util.spec_from_file_location("mgx_emu_build", os.path.join(ROOT, "tests", "emu", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return ctypes.CDLL(mod.build())
+    return emu_build.load()
 
 
 def _fp(a):

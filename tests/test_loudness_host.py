@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import emu_build
 import loudness_cases as cases
 import loudness_oracle as oracle
 from conftest import ROOT
@@ -23,10 +24,7 @@ P = ctypes.c_void_p
 
 @pytest.fixture(scope="module")
 def emu():
-    spec = importlib.util.spec_from_file_location("mgx_emu_loudness_build", os.path.join(ROOT, "tests", "emu", "build_loudness.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    lib = ctypes.CDLL(mod.build())
+    lib = emu_build.load("loudness")
     lib.emu_loudness.restype = ctypes.c_longlong
     lib.emu_loudness.argtypes = [P, ctypes.c_longlong, ctypes.c_int, P, P, P]
     lib.emu_loudness_geometry.argtypes = [ctypes.c_int, ctypes.c_longlong, P]

@@ -1,33 +1,26 @@
 """The library's device-free unit (csrc/mgx_policy.cpp) in a program of its own, without a GPU.
 
-Config validation, the delivery gain rule, the limiter's pass planner, loudness gating and the host FIR design's entry
-point are arithmetic on the structs of include/mgx.h; tests/test_delivery_host.py, test_tp_limiter_host.py and
-test_loudness_host.py check their values through libmgx.so.  Here the same unit is linked into a stand-alone driver
+Config validation, the delivery gain rule, the limiter's pass planner, loudness gating, the host FIR design's entry
+point and what the device entry points settle from their numbers alone are arithmetic on the structs of include/mgx.h;
+tests/test_delivery_host.py, test_tp_limiter_host.py, test_loudness_host.py, test_resample_plan.py and
+test_convert_rate_host.py check their values through libmgx.so.  Here the same unit is linked into a stand-alone driver
 (tests/emu/emu_policy_driver.cpp) that walks the edges those tests name, so that it can run under the sanitizers.
 """
 
-import importlib.util
-import os
 import re
 import subprocess
 
-from conftest import ROOT
+import emu_build
 
-GROUPS = ["check_config", "mgx_delivery_gain", "mgx_delivery_limit_step", "mgx_loudness_gate", "mgx_design_fir"]
-
-
-def _build_module():
-    spec = importlib.util.spec_from_file_location("mgx_emu_build", os.path.join(ROOT, "tests", "emu", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+GROUPS = ["check_config", "mgx_delivery_gain", "mgx_delivery_limit_step", "mgx_loudness_gate", "mgx_design_fir",
+          "resample_request", "stage_checks"]
 
 
 def test_standalone_driver_under_sanitizers(tmp_path):
     """Built with AddressSanitizer and UBSan, run once (nothing loaded into Python runs under a sanitizer): one line per
     group, every stated value met, exit status 0."""
     out = str(tmp_path / "driver")
-    _build_module().build_policy_driver(out, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    emu_build.build_driver("policy", out, ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
     done = subprocess.run([out], capture_output=True, text=True, timeout=60)
     assert done.returncode == 0, done.stdout + done.stderr
     lines = done.stdout.splitlines()

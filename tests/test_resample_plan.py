@@ -5,13 +5,11 @@ before it touches a handle, through the real libmgx.so.
 """
 
 import ctypes
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import emu_build
 from matchering_amd import _native
 from matchering_amd import resample as host
 
@@ -25,13 +23,10 @@ SHAPE = {(48000, 44100): (147, 160, 140), (44100, 48000): (160, 147, 130), (9600
 
 @pytest.fixture(scope="module")
 def emu():
-    spec = importlib.util.spec_from_file_location("mgx_emu_resample_build",
-                                                  os.path.join(ROOT, "tests", "emu", "build_resample.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    lib = ctypes.CDLL(mod.build())
+    lib = emu_build.load("resample")
     lib.emu_resample_length.restype = ctypes.c_longlong
     lib.emu_resample_length.argtypes = [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
+    lib.emu_resample_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p]
     lib.emu_resample.restype = ctypes.c_longlong
     lib.emu_resample.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.c_void_p, ctypes.c_void_p]
@@ -71,6 +66,24 @@ def test_plan_rows_are_the_prototypes(emu, sr, new):
     print(f"{sr} -> {new}: L {phases} M {hop} W {2 * taps}, max row difference {worst:.2e}")
     assert worst <= 2e-15
     assert row_sum == pytest.approx(float(np.abs(want).sum(axis=1).max()), rel=1e-12)
+
+
+@pytest.mark.parametrize("channels", [1, 2])
+@pytest.mark.parametrize("sr,new", PAIRS)
+def test_the_launch_is_the_geometrys(emu, sr, new, channels):
+    """What ``resample_launch`` gives ``mgx_resample`` and the emulation alike: LDS for the geometry's span, within what
+    a launch may ask for (RESAMPLE_SPAN_MAX stereo frames), and a workgroup per 256 outputs."""
+    geometry = (ctypes.c_int * 6)()
+    assert emu.emu_resample_geometry(sr, new, geometry) == 0
+    span, tile = geometry[5], 256
+    launch = (ctypes.c_longlong * 2)()
+    for n_out in (1, tile - 1, tile, tile + 1):
+        assert emu.emu_resample_launch(sr, new, channels, n_out, launch) == 0
+        grid, lds = launch
+        assert lds == span * channels * 4
+        assert lds <= 7680 * 8
+        assert grid == -(-n_out // tile), (n_out, grid)
+    assert emu.emu_resample_launch(44100, 44101, channels, 1, launch) == -1
 
 
 def test_output_length_is_pythons(emu):

@@ -6,7 +6,6 @@ file, and the Python surface.
 """
 
 import ctypes
-import importlib.util
 import math
 import os
 import re
@@ -15,6 +14,7 @@ import numpy as np
 import pytest
 
 import delivery_oracle
+import emu_build
 import loudness_oracle
 import matchering_amd as mg
 import tp_limiter_cases as cases
@@ -32,10 +32,7 @@ RATE = 44100
 
 @pytest.fixture(scope="module")
 def emu():
-    spec = importlib.util.spec_from_file_location("mgx_emu_tp_limit_build", os.path.join(ROOT, "tests", "emu", "build_tp_limit.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    lib = ctypes.CDLL(mod.build())
+    lib = emu_build.load("tp_limit")
     lib.emu_tp_limit_constants.argtypes = [ctypes.c_int, P]
     lib.emu_tp_limit.restype = ctypes.c_double
     lib.emu_tp_limit.argtypes = [P, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, P, P,
