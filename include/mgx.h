@@ -449,6 +449,57 @@ int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_rep
                             const double* pre_gain_db, const double* integrated, int32_t max_passes, double tolerance_lu,
                             mgx_delivery_limit_plan* next);
 
+/* Noise-shaped dither for CD-width deliveries: the quantiser's error is fed back through a short filter, so that the
+ * noise leaves the 2-5 kHz region, where the ear is most sensitive, for the top of the band.  Error feedback is a
+ * non-linear recurrence that no scan removes; it is defined here on SEGMENTS, so that a track is many short chains
+ * (DESIGN.md section 3.15).  With frames x[n][2], a gain, bits in {16, 24}, top = 2^(bits-1) - 1, a seed and a shaper
+ * c[1..K], 0 <= K <= MGX_SHAPER_TAPS_MAX (mgx_noise_shaper.c[k - 1] holds c[k]), per sample s = 2 m + ch:
+ *     a[s] = ((double)x[s] * gain) * top;     d[s] = U(s, 0) + U(s, 1)        exactly mgx_deliver's TPDF values
+ * Segment j covers the frames [j B, min(n, (j + 1) B)), B = MGX_SHAPER_SEGMENT; each channel of each segment is one chain.
+ * A chain starts at frame max(0, j B - W), W = MGX_SHAPER_WARMUP, with e_1 .. e_K = 0, and at every frame computes
+ *     t = 0.0;  for k = 1..K:  t = t + c[k] * e_k        (one product and one sum per tap, each rounded, in this order)
+ *     w = a - t;   r = rint(w + d);   e_new = r - w;   (e_K, .., e_1) <- (e_{K-1}, .., e_1, e_new)
+ *     for frames >= j B:  out = clip(r, -top - 1, top)   (the error is taken BEFORE the clip: |e| stays about 3/2)
+ * The warm-up frames j B - W .. j B - 1 are computed and not written.  The noise transfer function is
+ * H(z) = 1 - sum_k c[k] z^-k; with K = 0 the bytes are mgx_deliver's at dither 1.  Every value is defined bit for bit
+ * (tests/deliver_shaped_oracle.py).
+ * mgx_noise_shaper_preset hands out the library's table of published coefficients, designed for 44.1 kHz; host only:
+ *     id 1  Lipshitz, Vanderkooy, Wannamaker 1991, 5 taps:  2.033, -2.165, 1.959, -1.590, 0.6149
+ *     id 2  Wannamaker 1992, F-weighted, 9 taps:  2.412, -3.370, 3.937, -4.174, 3.353, -2.205, 1.281, -0.569, 0.0847
+ * for file rates from 44100 to 48000 Hz; MGX_ERR_UNSUPPORTED for every other rate, MGX_ERR_ARGUMENT for another id or a
+ * null `out`.  Custom coefficients are taken at any rate.
+ * Head-room.  Where nothing clips the file differs from a by e[n] - sum_k c[k] e[n-k] with |e| <= 3/2, plus float64
+ * rounding, so the shaped quantiser's e of mgx_delivery_gain's head-room A e / 2^(bits-1) is
+ *     e_shaped = (3/2) (1 + sum_k |c[k]|) (1 + 2^-20)
+ * -- the last factor covers every rounding of the recurrence whenever the policy accepts the ceiling at all (DESIGN.md
+ * section 3.15 has the derivation) -- and nothing clips under a ceiling <= 0 dBTP, since A > 1.
+ * mgx_delivery_gain_shaped is mgx_delivery_gain and mgx_delivery_limit_step_shaped is mgx_delivery_limit_step (its
+ * arguments plus the shaper), both with that head-room; delivery->dither must be 1 and delivery->bits 16 or 24.
+ * MGX_ERR_ARGUMENT, the message naming the field: what the plain functions refuse, a null shaper, taps outside
+ * [0, MGX_SHAPER_TAPS_MAX], a coefficient c[k] that is not finite.
+ * mgx_deliver_shaped: n_frames frames of x_dev -> 2 n_frames int16 or packed 24-bit samples in out_dev, in one launch
+ * (csrc/deliver_shaped_kernel.h); queued on the handle's stream, waits for nothing; n_frames == 0 succeeds and launches
+ * nothing.  MGX_ERR_ARGUMENT, the message naming the field: a null h, x_dev, shaper or out_dev; n_frames negative; x_dev
+ * or out_dev not 16-byte aligned; bits outside {16, 24}; taps outside [0, 16]; a coefficient or a gain that is not
+ * finite.  MGX_ERR_UNSUPPORTED: more than 536 million frames.  The handle is good for the next call. */
+#define MGX_SHAPER_TAPS_MAX 16
+#define MGX_SHAPER_SEGMENT 1024
+#define MGX_SHAPER_WARMUP 64
+typedef struct mgx_noise_shaper {
+    int32_t taps;                        /* K */
+    int32_t reserved;
+    double c[16];                        /* c[k - 1] = c[k] of the definition; entries from `taps` on are ignored */
+} mgx_noise_shaper;
+int mgx_noise_shaper_preset(int32_t id, int32_t sample_rate, mgx_noise_shaper* out);
+int mgx_delivery_gain_shaped(const mgx_delivery* delivery, const mgx_noise_shaper* shaper, const mgx_loudness_report* measured,
+                             mgx_delivery_result* result);
+int mgx_delivery_limit_step_shaped(const mgx_delivery* delivery, const mgx_noise_shaper* shaper,
+                                   const mgx_loudness_report* rendering, int32_t passes, const double* pre_gain_db,
+                                   const double* integrated, int32_t max_passes, double tolerance_lu,
+                                   mgx_delivery_limit_plan* next);
+int mgx_deliver_shaped(mgx_handle* h, const float* x_dev, int64_t n_frames, double gain, int32_t bits,
+                       const mgx_noise_shaper* shaper, uint64_t seed, void* out_dev);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

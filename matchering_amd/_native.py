@@ -139,10 +139,23 @@ class MgxDeliveryLimitPlan(ctypes.Structure):
     ]
 
 
+class MgxNoiseShaper(ctypes.Structure):
+    """mgx_noise_shaper (include/mgx.h)."""
+
+    _fields_ = [
+        ("taps", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("c", ctypes.c_double * 16),
+    ]
+
+
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
 PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
 LIMIT_PASSES_MAX = 16           # MGX_LIMIT_PASSES_MAX
+SHAPER_TAPS_MAX = 16            # MGX_SHAPER_TAPS_MAX
+SHAPER_SEGMENT = 1024           # MGX_SHAPER_SEGMENT
+SHAPER_WARMUP = 64              # MGX_SHAPER_WARMUP
 
 
 # every symbol include/mgx.h declares: name -> (restype, argtypes)
@@ -213,6 +226,14 @@ SYMBOLS = {
     "mgx_delivery_limit_step": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxLoudnessReport), ctypes.c_int32,
                                                c_double_p, c_double_p, ctypes.c_int32, ctypes.c_double,
                                                ctypes.POINTER(MgxDeliveryLimitPlan)]),
+    "mgx_noise_shaper_preset": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MgxNoiseShaper)]),
+    "mgx_delivery_gain_shaped": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxNoiseShaper),
+                                                ctypes.POINTER(MgxLoudnessReport), ctypes.POINTER(MgxDeliveryResult)]),
+    "mgx_delivery_limit_step_shaped": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxNoiseShaper),
+                                                      ctypes.POINTER(MgxLoudnessReport), ctypes.c_int32, c_double_p, c_double_p,
+                                                      ctypes.c_int32, ctypes.c_double, ctypes.POINTER(MgxDeliveryLimitPlan)]),
+    "mgx_deliver_shaped": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_double, ctypes.c_int32,
+                                          ctypes.POINTER(MgxNoiseShaper), ctypes.c_uint64, _VP]),
     "mgx_preview_cut": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_double, _VP]),
     "mgx_last_fir": (ctypes.c_int, [_VP, ctypes.POINTER(_VP), c_int32_p]),

@@ -29,8 +29,9 @@ and on a node with 8 GPUs::
 ``jobs.json`` is a list of ``{"target": path, "reference": path, "results": [{"file": path,
 "subtype": "PCM_16", "use_limiter": true, "normalize": true, "delivery": {"loudness": -14, "true_peak": -1,
 "dither": "tpdf_hp", "seed": 0, "limiter": true, "sample_rate": 48000}}, ...]}`` (``"delivery"`` and each of its keys
-optional: ``delivery.Delivery``; ``"limiter"``: ``true`` or the fields of ``delivery.TruePeakLimiter``; ``"sample_rate"``: the
-rate of that file in Hz, converted on the device, default the Config's internal rate); in place of ``"reference"`` a job may name a
+optional: ``delivery.Delivery``; ``"dither"``: a name -- "lipshitz5" and "wannamaker9" are noise shapers -- or
+``{"coefficients": [...]}`` for a ``delivery.NoiseShaper`` of one's own; ``"limiter"``: ``true`` or the fields of
+``delivery.TruePeakLimiter``; ``"sample_rate"``: the rate of that file in Hz, converted on the device, default the Config's internal rate); in place of ``"reference"`` a job may name a
 ``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
 list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).
 """

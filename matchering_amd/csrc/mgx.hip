@@ -29,6 +29,7 @@
 #include "resample_plan.h"
 #include "deliver_kernel.h"            // (behind every other kernel: it moves none of them in the code object)
 #include "tp_limit_kernel.h"
+#include "deliver_shaped_kernel.h"
 
 #include "mgx_policy.h"
 #include "handle.h"
@@ -515,6 +516,29 @@ int mgx_deliver(mgx_handle* h, const float* x_dev, int64_t samples, double gain,
     a.x = x_dev;
     a.out = out_dev;
     hipLaunchKernelGGL(k_deliver, dim3((unsigned)deliver_grid(samples)), dim3(DELIVER_THREADS), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int mgx_deliver_shaped(mgx_handle* h, const float* x_dev, int64_t n_frames, double gain, int32_t bits,
+                       const mgx_noise_shaper* shaper, uint64_t seed, void* out_dev) {
+    static_assert(SHAPED_TAPS_MAX == MGX_SHAPER_TAPS_MAX && MGX_SHAPER_SEGMENT % SHAPED_STEP == 0 &&
+                      MGX_SHAPER_WARMUP % SHAPED_STEP == 0 && SHAPED_STEP % 2 == 0,
+                  "a step of k_deliver_shaped is whole frame pairs and divides the segment and the warm-up");
+    MGX_TRY(deliver_shaped_check(n_frames, gain, bits, shaper));
+    if (!h) return fail(MGX_ERR_ARGUMENT, "h: null handle");
+    if (!x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
+    if (!out_dev) return fail(MGX_ERR_ARGUMENT, "out_dev: null");
+    if (((size_t)x_dev) & 15) return fail(MGX_ERR_ARGUMENT, "x_dev: must be 16-byte aligned");
+    if (((size_t)out_dev) & 15) return fail(MGX_ERR_ARGUMENT, "out_dev: must be 16-byte aligned");
+    if (n_frames == 0) return 0;
+    MGX_TRY(open_main(h));
+    DeliverShapedArgs a;
+    deliver_shaped_launch(a, n_frames, gain, bits, shaper->taps, shaper->c, MGX_SHAPER_SEGMENT, MGX_SHAPER_WARMUP, seed);
+    a.x = x_dev;
+    a.out = out_dev;
+    hipLaunchKernelGGL(k_deliver_shaped, dim3((unsigned)shaped_grid(n_frames, MGX_SHAPER_SEGMENT)), dim3(SHAPED_THREADS), 0,
+                       h->stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }

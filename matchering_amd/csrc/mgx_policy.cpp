@@ -120,6 +120,36 @@ int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither) {
     return 0;
 }
 
+int shaper_check(const mgx_noise_shaper* shaper) {
+    if (!shaper) return fail(MGX_ERR_ARGUMENT, "shaper: null");
+    if (shaper->taps < 0 || shaper->taps > MGX_SHAPER_TAPS_MAX)
+        return fail(MGX_ERR_ARGUMENT, "taps: outside [0, " + std::to_string(MGX_SHAPER_TAPS_MAX) + "]");
+    for (int k = 0; k < shaper->taps; ++k)
+        if (!std::isfinite(shaper->c[k])) return fail(MGX_ERR_ARGUMENT, "c[" + std::to_string(k + 1) + "]: not a finite number");
+    return 0;
+}
+
+static int shaped_bits_check(int32_t bits) {
+    if (bits != 16 && bits != 24) return fail(MGX_ERR_ARGUMENT, "bits: a noise-shaped delivery is 16 or 24-bit PCM");
+    return 0;
+}
+
+int deliver_shaped_check(int64_t n_frames, double gain, int32_t bits, const mgx_noise_shaper* shaper) {
+    MGX_TRY(shaped_bits_check(bits));
+    MGX_TRY(shaper_check(shaper));
+    if (n_frames < 0) return fail(MGX_ERR_ARGUMENT, "n_frames: negative");
+    if (!std::isfinite(gain)) return fail(MGX_ERR_ARGUMENT, "gain: not a finite number");
+    return check_length(n_frames);
+}
+
+// what the _shaped policy functions ask of their delivery and shaper
+static int shaped_policy_check(const mgx_delivery* delivery, const mgx_noise_shaper* shaper) {
+    MGX_TRY(shaper_check(shaper));
+    MGX_TRY(shaped_bits_check(delivery->bits));
+    if (delivery->dither != 1) return fail(MGX_ERR_ARGUMENT, "dither: a noise-shaped delivery is dithered with TPDF (1)");
+    return 0;
+}
+
 int tp_limit_check(int64_t n, double pre_gain, double ceiling, int32_t lookahead, double release) {
     if (n < 0) return fail(MGX_ERR_ARGUMENT, "n: negative");
     if (!std::isfinite(pre_gain) || pre_gain <= 0.0) return fail(MGX_ERR_ARGUMENT, "pre_gain: must be finite and positive");
@@ -154,7 +184,8 @@ int profile_merge_check(const void* const* profiles_dev, const int32_t* weights,
 }
 
 // the numerator of g_peak: the linear ceiling less the quantiser's head-room (mgx_delivery_limit_step's ceiling is the same number)
-static int delivery_room(const mgx_delivery* delivery, double* room_out) {
+// `shaper`: null for the plain quantiser, else the error feedback's (include/mgx.h: e_shaped)
+static int delivery_room(const mgx_delivery* delivery, const mgx_noise_shaper* shaper, double* room_out) {
     // A: the most the meter's interpolator makes of errors of magnitude 1 -- the largest per-phase sum of |taps|
     double taps[49], A = 0.0;
     loudness_true_peak_taps(taps);
@@ -163,7 +194,7 @@ static int delivery_room(const mgx_delivery* delivery, double* room_out) {
         for (int k = p; k < 49; k += 4) sum += std::fabs(taps[k]);
         A = std::max(A, sum);
     }
-    const double e = delivery->bits == 0 ? 0.0 : (delivery->dither ? 1.5 : 0.5);
+    const double e = delivery->bits == 0 ? 0.0 : shaper ? shaper_error_lsb(*shaper) : (delivery->dither ? 1.5 : 0.5);
     const double margin = delivery->bits == 0 ? 0.0 : A * e / std::ldexp(1.0, delivery->bits - 1);
     const double room = std::pow(10.0, delivery->ceiling_dbtp / 20.0) - margin;
     if (!(room > 0.0))
@@ -226,7 +257,9 @@ int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_ra
     return 0;
 }
 
-int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* measured, mgx_delivery_result* result) {
+// mgx_delivery_gain (shaper null) and mgx_delivery_gain_shaped
+static int delivery_gain(const mgx_delivery* delivery, const mgx_noise_shaper* shaper, const mgx_loudness_report* measured,
+                         mgx_delivery_result* result) {
     if (!delivery || !measured || !result) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(deliver_format_check(delivery->bits, delivery->dither));
     const double target = delivery->target_lufs, ceiling = delivery->ceiling_dbtp;
@@ -242,7 +275,7 @@ int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* m
     double g_peak = INFINITY;
     if (!std::isnan(ceiling)) {
         double room;
-        MGX_TRY(delivery_room(delivery, &room));
+        MGX_TRY(delivery_room(delivery, shaper, &room));
         if (peak > 0.0) g_peak = room / peak;
     }
     const double gain = std::min(g_loud, g_peak);
@@ -256,9 +289,10 @@ int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* m
     return 0;
 }
 
-int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_report* rendering, int32_t passes,
-                            const double* pre_gain_db, const double* integrated, int32_t max_passes, double tolerance_lu,
-                            mgx_delivery_limit_plan* next) {
+// mgx_delivery_limit_step (shaper null) and mgx_delivery_limit_step_shaped
+static int delivery_limit_step(const mgx_delivery* delivery, const mgx_noise_shaper* shaper, const mgx_loudness_report* rendering,
+                               int32_t passes, const double* pre_gain_db, const double* integrated, int32_t max_passes,
+                               double tolerance_lu, mgx_delivery_limit_plan* next) {
     if (!delivery || !rendering || !next) return fail(MGX_ERR_ARGUMENT, "null argument");
     if (max_passes < 1 || max_passes > MGX_LIMIT_PASSES_MAX)
         return fail(MGX_ERR_ARGUMENT, "max_passes: outside [1, " + std::to_string(MGX_LIMIT_PASSES_MAX) + "]");
@@ -267,11 +301,11 @@ int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_rep
     if (passes > 0 && (!pre_gain_db || !integrated)) return fail(MGX_ERR_ARGUMENT, "pre_gain_db / integrated: null with passes run");
     if (std::isnan(delivery->ceiling_dbtp)) return fail(MGX_ERR_ARGUMENT, "ceiling_dbtp: a limiter needs a ceiling");
     mgx_delivery_result linear;
-    MGX_TRY(mgx_delivery_gain(delivery, rendering, &linear));
+    MGX_TRY(delivery_gain(delivery, shaper, rendering, &linear));
     next->run = 0;
     next->reserved = 0;
     next->pre_gain_db = passes > 0 ? pre_gain_db[passes - 1] : 0.0;
-    MGX_TRY(delivery_room(delivery, &next->ceiling));
+    MGX_TRY(delivery_room(delivery, shaper, &next->ceiling));
     const double target = delivery->target_lufs;
     const bool has_target = !std::isnan(target) && std::isfinite(rendering->integrated);
     if (passes == 0) {
@@ -293,6 +327,49 @@ int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_rep
     next->run = 1;
     next->pre_gain_db = p + (target - loud) / slope;
     return 0;
+}
+
+int mgx_delivery_gain(const mgx_delivery* delivery, const mgx_loudness_report* measured, mgx_delivery_result* result) {
+    return delivery_gain(delivery, nullptr, measured, result);
+}
+
+int mgx_delivery_limit_step(const mgx_delivery* delivery, const mgx_loudness_report* rendering, int32_t passes,
+                            const double* pre_gain_db, const double* integrated, int32_t max_passes, double tolerance_lu,
+                            mgx_delivery_limit_plan* next) {
+    return delivery_limit_step(delivery, nullptr, rendering, passes, pre_gain_db, integrated, max_passes, tolerance_lu, next);
+}
+
+// ---- noise-shaped deliveries ----------------------------------------------------
+int mgx_noise_shaper_preset(int32_t id, int32_t sample_rate, mgx_noise_shaper* out) {
+    if (!out) return fail(MGX_ERR_ARGUMENT, "out: null");
+    for (const ShaperPreset& preset : SHAPER_PRESETS) {
+        if (preset.id != id) continue;
+        if (sample_rate < SHAPER_PRESET_RATE_MIN || sample_rate > SHAPER_PRESET_RATE_MAX)
+            return fail(MGX_ERR_UNSUPPORTED, "sample_rate: the noise shaper '" + std::string(preset.name) + "' is designed for 44100 Hz and is handed out for " +
+                                             std::to_string(SHAPER_PRESET_RATE_MIN) + " to " + std::to_string(SHAPER_PRESET_RATE_MAX) +
+                                             " Hz, not " + std::to_string(sample_rate) + " Hz (custom coefficients are taken at any rate)");
+        std::memset(out, 0, sizeof(*out));
+        out->taps = preset.taps;
+        for (int k = 0; k < preset.taps; ++k) out->c[k] = preset.c[k];
+        return 0;
+    }
+    return fail(MGX_ERR_ARGUMENT, "id: no such noise shaper preset (1: lipshitz5, 2: wannamaker9)");
+}
+
+int mgx_delivery_gain_shaped(const mgx_delivery* delivery, const mgx_noise_shaper* shaper, const mgx_loudness_report* measured,
+                             mgx_delivery_result* result) {
+    if (!delivery || !measured || !result) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(shaped_policy_check(delivery, shaper));
+    return delivery_gain(delivery, shaper, measured, result);
+}
+
+int mgx_delivery_limit_step_shaped(const mgx_delivery* delivery, const mgx_noise_shaper* shaper,
+                                   const mgx_loudness_report* rendering, int32_t passes, const double* pre_gain_db,
+                                   const double* integrated, int32_t max_passes, double tolerance_lu,
+                                   mgx_delivery_limit_plan* next) {
+    if (!delivery || !rendering || !next) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(shaped_policy_check(delivery, shaper));
+    return delivery_limit_step(delivery, shaper, rendering, passes, pre_gain_db, integrated, max_passes, tolerance_lu, next);
 }
 
 // ---- reference profiles -------------------------------------------------------

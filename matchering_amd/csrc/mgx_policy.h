@@ -1,6 +1,7 @@
 // The part of libmgx.so that touches no device (mgx_policy.cpp): the calling thread's error text, the validation of a
 // Config, the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
-// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_delivery_gain, mgx_delivery_limit_step, mgx_profile_bytes --
+// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
+// mgx_noise_shaper_preset, mgx_profile_bytes --
 // and what the device entry points settle from their numbers alone before they touch a handle.
 // No HIP here: g++ compiles the unit by itself (tests/emu/emu_policy_driver.cpp runs it under the sanitizers), and
 // mgx.hip uses what is declared below.
@@ -12,6 +13,7 @@
 #include "../../include/mgx.h"
 #include "fir_design.h"
 #include "loudness_plan.h"
+#include "noise_shaper.h"
 #include "resample_plan.h"
 
 namespace mgx {
@@ -42,6 +44,9 @@ int resample_request(const char* entry, const char* subject, const int32_t* chan
 int loudness_request(const mgx_loudness_report* report, int64_t n, int32_t sample_rate, const double* sub_energy,
                      int64_t capacity, int64_t* count, int* S);
 int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither);
+// a shaper as every entry point that takes one accepts it, and mgx_deliver_shaped's numbers
+int shaper_check(const mgx_noise_shaper* shaper);
+int deliver_shaped_check(int64_t n_frames, double gain, int32_t bits, const mgx_noise_shaper* shaper);
 // (the ranges include/mgx.h documents; mgx.hip holds tp_limit_kernel.h's constants to them)
 constexpr int TP_LIMIT_LOOKAHEAD_MAX = 2048;
 constexpr double TP_LIMIT_RELEASE_MAX = 4194304.0;             // 2^22 frames

@@ -27,15 +27,26 @@ above, which then runs on the converted frames at that rate, so the ceiling hold
 at.
 
     mg.pcm24("video.wav", delivery=mg.Delivery(loudness=-14.0, true_peak=-1.0, sample_rate=48000))
+
+A 16 or 24-bit delivery may be NOISE-SHAPED: ``dither`` names a preset ("lipshitz5", "wannamaker9": published
+error-feedback filters for 44.1 kHz, handed out for file rates of 44.1 to 48 kHz) or is a ``NoiseShaper`` with
+coefficients of its own.  The TPDF-dithered quantiser's error is then fed back through that filter
+(``mgx_deliver_shaped``), which moves the noise out of the 2-5 kHz region; the gain leaves the larger head-room such a
+quantiser needs (``mgx_delivery_gain_shaped``), so the ceiling holds as before.
+
+    mg.pcm16("cd.wav", delivery=mg.Delivery(true_peak=-1.0, dither="wannamaker9"))
 """
 
 import ctypes
 import math
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, field, fields
+from functools import lru_cache
 
 from .loudness import Loudness, _db
 
 DITHERS = {None: 0, "tpdf": 1, "tpdf_hp": 2}
+SHAPER_PRESETS = {"lipshitz5": 1, "wannamaker9": 2}                  # the ids of mgx_noise_shaper_preset
+SHAPER_TAPS_MAX = 16                                                 # MGX_SHAPER_TAPS_MAX
 SUBTYPE_BITS = {"PCM_16": 16, "PCM_24": 24, "PCM_32": 32}            # every other subtype is delivered as float32 frames
 LIMITED_BY = (None, "loudness", "true_peak")
 
@@ -96,9 +107,80 @@ class TruePeakLimiter:
 
 
 @dataclass(frozen=True)
+class NoiseShaper:
+    """The error-feedback filter of a noise-shaped delivery: ``coefficients`` c[1..K], K at most 16, of the noise transfer
+    function H(z) = 1 - sum c[k] z^-k (include/mgx.h, ``mgx_noise_shaper``).  ``preset`` is not an argument: it is the
+    name of the library's preset on what ``NoiseShaper.lipshitz5()`` / ``.wannamaker9()`` return -- their coefficients come
+    from the library's table -- and None on coefficients of one's own, which are taken at any file rate."""
+
+    coefficients: tuple
+    preset: str = field(default=None, init=False)
+
+    def __post_init__(self):
+        try:
+            values = tuple(self.coefficients)
+        except TypeError:
+            raise ValueError(f"NoiseShaper: coefficients must be a sequence of numbers, got {self.coefficients!r}") from None
+        for value in values:
+            if isinstance(value, bool) or not (isinstance(value, (int, float)) and math.isfinite(value)):
+                raise ValueError(f"NoiseShaper: every coefficient must be a finite number, got {value!r}")
+        if len(values) > SHAPER_TAPS_MAX:
+            raise ValueError(f"NoiseShaper: at most {SHAPER_TAPS_MAX} coefficients, got {len(values)}")
+        object.__setattr__(self, "coefficients", tuple(float(v) for v in values))
+
+    @classmethod
+    def lipshitz5(cls):
+        """Lipshitz, Vanderkooy, Wannamaker 1991: 5 taps for 44.1 kHz (the library's preset 1)."""
+        return preset_shaper("lipshitz5")
+
+    @classmethod
+    def wannamaker9(cls):
+        """Wannamaker 1992, F-weighted: 9 taps for 44.1 kHz (the library's preset 2)."""
+        return preset_shaper("wannamaker9")
+
+    def native(self):
+        from ._native import MgxNoiseShaper
+
+        out = MgxNoiseShaper()
+        out.taps = len(self.coefficients)
+        for k, value in enumerate(self.coefficients):
+            out.c[k] = value
+        return out
+
+    def __str__(self):
+        return self.preset if self.preset is not None else f"noise-shaped, {len(self.coefficients)} taps"
+
+
+@lru_cache(maxsize=None)
+def preset_shaper(name):
+    """The ``NoiseShaper`` of the library's preset ``name``, its coefficients read from the library's one table
+    (``mgx_noise_shaper_preset``) the first time it is asked for.  Needs no GPU."""
+    from . import _native
+
+    out = _native.MgxNoiseShaper()
+    _native.check(_native.library().mgx_noise_shaper_preset(SHAPER_PRESETS[name], 44100, ctypes.byref(out)))
+    shaper = NoiseShaper(tuple(out.c[:out.taps]))
+    object.__setattr__(shaper, "preset", name)
+    return shaper
+
+
+def check_preset_rate(name, rate):
+    """``ValueError`` where the library does not hand the preset ``name`` out for a file at ``rate`` Hz
+    (``mgx_noise_shaper_preset``).  Needs no GPU."""
+    from . import _native
+
+    rc = _native.library().mgx_noise_shaper_preset(SHAPER_PRESETS[name], int(rate), ctypes.byref(_native.MgxNoiseShaper()))
+    if rc == _native.ERR_UNSUPPORTED:
+        raise ValueError(f"a delivery at {rate} Hz cannot be shaped with '{name}': "
+                         + _native.library().mgx_last_error().decode("utf-8", "replace"))
+    _native.check(rc)
+
+
+@dataclass(frozen=True)
 class Delivery:
     """What a result is to meet.  ``loudness``: integrated loudness in LUFS, ``true_peak``: the ceiling in dBTP (at most
-    0), either may be None; ``dither``: None, "tpdf" or "tpdf_hp" (high-passed TPDF), for 16 and 24-bit files;
+    0), either may be None; ``dither``: None, "tpdf" or "tpdf_hp" (high-passed TPDF), or noise-shaped TPDF -- "lipshitz5",
+    "wannamaker9" or a ``NoiseShaper`` -- for 16 and 24-bit files;
     ``seed``: the dither generator's key -- the same seed writes the same file; ``limiter``: a ``TruePeakLimiter`` to run
     where the ceiling keeps the linear gain under the target (it needs ``true_peak``), None for the linear gain alone;
     ``sample_rate``: the rate of the written file in Hz -- the rendering is converted in HBM (``mgx_convert_rate``)
@@ -119,8 +201,10 @@ class Delivery:
                 raise ValueError(f"Delivery: {name} must be a finite number or None, got {value!r}")
         if self.true_peak is not None and self.true_peak > 0.0:
             raise ValueError(f"Delivery: a true-peak ceiling above 0 dBTP would clip, got {self.true_peak!r}")
-        if self.dither not in DITHERS:
-            raise ValueError(f"Delivery: dither must be None, 'tpdf' or 'tpdf_hp', got {self.dither!r}")
+        if not isinstance(self.dither, NoiseShaper) and not (
+                (self.dither is None or isinstance(self.dither, str)) and (self.dither in DITHERS or self.dither in SHAPER_PRESETS)):
+            raise ValueError("Delivery: dither must be None, 'tpdf', 'tpdf_hp', 'lipshitz5', 'wannamaker9' or a NoiseShaper, "
+                             f"got {self.dither!r}")
         if not (isinstance(self.seed, int) and 0 <= self.seed < 2 ** 64):
             raise ValueError(f"Delivery: seed must be an integer in [0, 2**64), got {self.seed!r}")
         if self.limiter is not None:
@@ -138,6 +222,23 @@ class Delivery:
         """The rate of the written file: ``sample_rate``, or the Config's internal rate where it is None."""
         return int(internal_rate) if self.sample_rate is None else self.sample_rate
 
+    @property
+    def shaper(self):
+        """The ``NoiseShaper`` of a noise-shaped delivery (a preset's from the library's table), else None."""
+        if isinstance(self.dither, NoiseShaper):
+            return self.dither
+        return preset_shaper(self.dither) if self.dither in SHAPER_PRESETS else None
+
+    @property
+    def shaped(self):
+        return isinstance(self.dither, NoiseShaper) or self.dither in SHAPER_PRESETS
+
+    def check_shaper_rate(self, internal_rate):
+        """``ValueError`` for a preset shaper at a file rate it is not handed out for.  Needs no GPU."""
+        shaper = self.shaper
+        if shaper is not None and shaper.preset is not None:
+            check_preset_rate(shaper.preset, self.rate(internal_rate))
+
     def check_subtype(self, subtype):
         """The error ``Result`` raises at construction for a width this delivery cannot be written at."""
         if self.dither is not None and subtype not in ("PCM_16", "PCM_24"):
@@ -148,12 +249,13 @@ class Delivery:
 
         return MgxDelivery(math.nan if self.loudness is None else float(self.loudness),
                            math.nan if self.true_peak is None else float(self.true_peak), int(bits),
-                           DITHERS[self.dither], int(self.seed))
+                           1 if self.shaped else DITHERS[self.dither], int(self.seed))     # (a shaper's dither is TPDF)
 
     @classmethod
     def from_json(cls, entry):
         """``{"loudness": ..., "true_peak": ..., "dither": ..., "seed": ..., "limiter": ..., "sample_rate": ...}`` of a
-        batch job (every key optional; ``"limiter"``: ``true`` for ``TruePeakLimiter()``, or an object with its fields)."""
+        batch job (every key optional; ``"limiter"``: ``true`` for ``TruePeakLimiter()``, or an object with its fields;
+        ``"dither"``: a name, ``{"coefficients": [...]}`` for a ``NoiseShaper`` of one's own, or such an object itself)."""
         if isinstance(entry, cls):
             return entry
         if not isinstance(entry, dict):
@@ -161,6 +263,12 @@ class Delivery:
         unknown = set(entry) - {"loudness", "true_peak", "dither", "seed", "limiter", "sample_rate"}
         if unknown:
             raise ValueError(f"delivery: unknown keys {sorted(unknown)}")
+        if isinstance(entry.get("dither"), dict):
+            if set(entry["dither"]) != {"coefficients"} or not isinstance(entry["dither"]["coefficients"], list):
+                raise ValueError(f"delivery: a dither object is {{\"coefficients\": [...]}}, got {entry['dither']!r}")
+            entry = {**entry, "dither": NoiseShaper(tuple(entry["dither"]["coefficients"]))}
+        elif isinstance(entry.get("dither"), list):
+            raise ValueError(f"delivery: dither is a name or {{\"coefficients\": [...]}}, got {entry['dither']!r}")
         if entry.get("limiter") in (None, False):
             return cls(**{key: value for key, value in entry.items() if key != "limiter"})
         return cls(**{**entry, "limiter": TruePeakLimiter.from_json(entry["limiter"])})
@@ -205,7 +313,7 @@ class Delivered:
     def __str__(self):
         text = (f"gain {self.gain_db:+.2f} dB: {self.achieved_lufs:.2f} LUFS, true peak {self.achieved_true_peak_db:.2f} dBTP "
                 f"({'float32' if self.bits == 0 else f'{self.bits} bit'}"
-                f"{'' if self.delivery.dither is None else ', ' + self.delivery.dither})")
+                f"{'' if self.delivery.dither is None else ', ' + str(self.delivery.dither)})")
         if self.sample_rate is not None and self.sample_rate != self.internal_rate:
             text += f" at {self.sample_rate} Hz"
         if self.limiter_passes > 0:
@@ -218,14 +326,19 @@ class Delivered:
 
 def delivery_gain(delivery: Delivery, bits: int, measured: Loudness) -> Delivered:
     """``mgx_delivery_gain`` (host only, needs no GPU): the gain that brings a rendering measured as ``measured`` to
-    ``delivery`` at ``bits`` (0: float32)."""
+    ``delivery`` at ``bits`` (0: float32); ``mgx_delivery_gain_shaped`` for a noise-shaped delivery."""
     from . import _native
 
     report = _native.MgxLoudnessReport()
     report.integrated, report.true_peak = measured.integrated, measured.true_peak
     out = _native.MgxDeliveryResult()
-    _native.check(_native.library().mgx_delivery_gain(ctypes.byref(delivery.native(bits)), ctypes.byref(report),
-                                                      ctypes.byref(out)))
+    shaper = delivery.shaper
+    if shaper is None:
+        _native.check(_native.library().mgx_delivery_gain(ctypes.byref(delivery.native(bits)), ctypes.byref(report),
+                                                          ctypes.byref(out)))
+    else:
+        _native.check(_native.library().mgx_delivery_gain_shaped(ctypes.byref(delivery.native(bits)), ctypes.byref(shaper.native()),
+                                                                 ctypes.byref(report), ctypes.byref(out)))
     return Delivered(out.gain, out.achieved_lufs, out.achieved_true_peak, out.shortfall_lu, LIMITED_BY[out.limited_by],
                      measured, delivery, int(bits))
 
@@ -239,8 +352,9 @@ def _report(measured):
 
 
 def limit_step(delivery: Delivery, bits: int, measured: Loudness, pre_gains_db=(), integrated=()):
-    """``mgx_delivery_limit_step`` (host only, needs no GPU): ``(run, pre_gain_db, ceiling)`` after the passes whose
-    pre-gains (dB) and integrated loudness are given -- none yet: whether the limiter is needed at all."""
+    """``mgx_delivery_limit_step`` (host only, needs no GPU; ``mgx_delivery_limit_step_shaped`` for a noise-shaped
+    delivery): ``(run, pre_gain_db, ceiling)`` after the passes whose pre-gains (dB) and integrated loudness are given --
+    none yet: whether the limiter is needed at all."""
     from . import _native
 
     if delivery.limiter is None:
@@ -250,9 +364,14 @@ def limit_step(delivery: Delivery, bits: int, measured: Loudness, pre_gains_db=(
         raise ValueError("limit_step: one integrated loudness per pass")
     array = ctypes.c_double * max(passes, 1)
     plan = _native.MgxDeliveryLimitPlan()
-    _native.check(_native.library().mgx_delivery_limit_step(
-        ctypes.byref(delivery.native(bits)), ctypes.byref(_report(measured)), passes, array(*map(float, pre_gains_db)),
-        array(*map(float, integrated)), int(delivery.limiter.max_passes), float(delivery.limiter.tolerance_lu), ctypes.byref(plan)))
+    rest = (ctypes.byref(_report(measured)), passes, array(*map(float, pre_gains_db)), array(*map(float, integrated)),
+            int(delivery.limiter.max_passes), float(delivery.limiter.tolerance_lu), ctypes.byref(plan))
+    shaper = delivery.shaper
+    if shaper is None:
+        _native.check(_native.library().mgx_delivery_limit_step(ctypes.byref(delivery.native(bits)), *rest))
+    else:
+        _native.check(_native.library().mgx_delivery_limit_step_shaped(ctypes.byref(delivery.native(bits)),
+                                                                       ctypes.byref(shaper.native()), *rest))
     return bool(plan.run), plan.pre_gain_db, plan.ceiling
 
 
@@ -294,11 +413,13 @@ class DeliveryRequest:
     def check_rates(self, internal_rate, frames=0):
         """``{rate: frames of a rendering of ``frames`` frames converted to it}`` for every delivery rate other than
         ``internal_rate``; ``ValueError`` naming both rates and the library's reason for a pair ``mgx_convert_rate``
-        refuses.  Needs no GPU (the entry point's device-free form): ``process`` calls it before any audio is loaded."""
+        refuses, or a preset noise shaper and the file rate ``mgx_noise_shaper_preset`` does not hand it out for.  Needs
+        no GPU (the entry points' device-free forms): ``process`` calls it before any audio is loaded."""
         from .device import delivery_length
 
         lengths = {}
         for _, _, _, delivery in self.items:
+            delivery.check_shaper_rate(internal_rate)
             rate = delivery.rate(internal_rate)
             if rate != internal_rate and rate not in lengths:
                 lengths[rate] = delivery_length(frames, internal_rate, rate)

@@ -474,6 +474,25 @@ class Device:
             self.synchronize()
         return out
 
+    def deliver_shaped(self, buf, frames, gain, bits, shaper, seed=0, wait=True):
+        """(frames, 2) float32 in HBM -> a noise-shaped 16 or 24-bit rendition on the host (pinned), in one launch
+        (``mgx_deliver_shaped``): every sample times ``gain``, TPDF-dithered (keyed by ``seed``), quantised with the error
+        fed back through ``shaper`` (a ``delivery.NoiseShaper``) and packed -- int16 (n, 2), or uint8 (n, 6) for packed
+        24-bit."""
+        nbytes = int(frames) * 2 * (int(bits) // 8)
+        out_dev = DeviceBuffer(self, max(nbytes, 1))
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        try:
+            check(library().mgx_deliver_shaped(self.handle, ctypes.c_void_p(ptr), int(frames), float(gain), int(bits),
+                                               ctypes.byref(shaper.native()), int(seed), ctypes.c_void_p(out_dev.ptr)))
+            shape, dtype = {16: ((frames, 2), np.int16), 24: ((frames, 6), np.uint8)}[int(bits)]
+            out = self.download(out_dev, shape, dtype, wait=False)
+        finally:
+            out_dev.release()   # (recycled by later work on this stream only, which is ordered behind the copy)
+        if wait:
+            self.synchronize()
+        return out
+
     def tp_limit(self, buf, frames, pre_gain, ceiling, lookahead, release, out=None, reduction=True):
         """The deliveries' true-peak look-ahead limiter on (frames, 2) float32 in HBM (``mgx_tp_limit``): pre-gain and
         ceiling linear, look-ahead and release in frames.  Returns ``(out, max_reduction)``: the limited frames in a new

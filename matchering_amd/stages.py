@@ -47,7 +47,8 @@ def _is_profile(reference):
 def _limited(dev, rendering, n, rate, delivery, bits, measured):
     """The passes of a delivery's limiter (``mgx_tp_limit``, each from the rendering itself, each metered) as
     ``mgx_delivery_limit_step`` asks for them: ``(Delivered, the last pass's frames)``, or None where it asks for none.
-    The record is ``mgx_delivery_gain``'s on the measurement of those frames."""
+    The record is ``mgx_delivery_gain``'s on the measurement of those frames (for a noise-shaped delivery both are the
+    ``_shaped`` entry points: ``delivery.limit_step`` and ``delivery.delivery_gain`` choose)."""
     from dataclasses import replace
 
     from .delivery import delivery_gain, limit_step
@@ -94,6 +95,7 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # mgx_deliver), made while the renderings are still in HBM and left in the request; a rendering that only a delivery
     # names is computed but not returned, and ``loudness`` also receives ("delivered:" + key, delivery.Delivered).  A
     # delivery that carries a limiter and whose ceiling binds is limited first (mgx_tp_limit, mgx_delivery_limit_step).  A
+    # noise-shaped delivery takes the _shaped policy and mgx_deliver_shaped in their place.  A
     # delivery at another ``sample_rate`` than the internal one is made from the rendering converted to that rate in HBM
     # (mgx_convert_rate) and measured there; the renderings returned, the previews and the other callbacks do not change.)
     dev = device if device is not None else default_device()
@@ -193,8 +195,12 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                         deliveries.delivered[key] = record
                         # queued behind the measurement; the array is valid after the one wait below
                         try:
-                            deliveries.arrays[key] = dev.deliver(frames, length, 2, record.gain, bits, DITHERS[delivery.dither],
-                                                                 delivery.seed, wait=False)
+                            if delivery.shaped:          # (the policy above was the _shaped one: delivery.delivery_gain)
+                                deliveries.arrays[key] = dev.deliver_shaped(frames, length, record.gain, bits, delivery.shaper,
+                                                                            delivery.seed, wait=False)
+                            else:
+                                deliveries.arrays[key] = dev.deliver(frames, length, 2, record.gain, bits,
+                                                                     DITHERS[delivery.dither], delivery.seed, wait=False)
                         finally:
                             if limited is not None:
                                 frames.release() # (recycled by later work on this stream only, which is ordered behind the kernel)
