@@ -161,6 +161,49 @@ int mgx_analyze(mgx_handle* h, const float* x_dev, int64_t n, const mgx_config* 
 int mgx_design_fir(const mgx_config* cfg, const double* avg_target, const double* avg_reference,
                    double* taps, double* curve_raw, double* curve_smooth);
 
+/* Matching EQ controls: how much of the matching curve is applied, how far it may boost and cut, and the phase of the FIR
+ * (get_fir, match_frequencies.py:78-101, has none of this: one linear-phase FIR from the whole curve).  Part of the new
+ * surface.  With s[k], k = 0 .. F/2, a channel's smoothed curve (match_frequencies.py:45-75, bins 0 and 1 pinned):
+ *   1. shape, float64, for k >= 1:
+ *          d = amount * 20 log10(max(s[k], min_value));   d = min(d, max_boost_db);   d = max(d, -max_cut_db)
+ *          s'[k] = 10^(d / 20);    s'[0] = 0
+ *      A NaN cap is no cap.  With amount == 1 and no cap the stage is skipped, not multiplied by one.  Level matching is
+ *      untouched: rms_coefficient and the correction rounds still bring the result to the reference's RMS.
+ *   2. linear-phase taps lin[0 .. F): the existing synthesis (irfft, ifftshift, Hann) on s', float32 in the handle.
+ *   3. phase == 1, minimum phase, with N = 4F, float64:
+ *          H[m] = |DFT_N(lin, zero padded)[m]|;   L[m] = ln(max(H[m], 1e-9 max H));   c = Re IDFT_N(L)
+ *          fold: c[0] and c[N/2] stay, c[1 .. N/2) doubles, c(N/2 .. N) = 0;   g = Re IDFT_N(exp(DFT_N(c)))
+ *          taper[j] = 1 for j < F/4,  (1 + cos(pi (j - F/4) / (F/4))) / 2 for F/4 <= j < F/2
+ *          taps[F/2 + j] = g[j] taper[j] for j < F/2,   taps[k] = 0 for k < F/2;   one rounding to float32 at the store
+ *      The response starts where the linear-phase FIR peaks: the result stays time-aligned with a linear-phase master
+ *      of the same pair, and nothing precedes the main tap.
+ * mgx_eq_shape_check: needs no GPU.  MGX_ERR_ARGUMENT, the message naming the field: a null argument, amount outside
+ * [0, 2] or not finite, a cap that is negative or infinite, phase outside {0, 1}, reserved != 0.  MGX_ERR_UNSUPPORTED,
+ * the size named: phase == 1 with fft_size below 64 or above 16384 (the chain runs N = 4F points per channel through
+ * one call's scratch; 32768 and 65536 are not instantiated).
+ * mgx_shape_fir: steps 1 to 3 on the host in float64 from a smoothed curve (mgx_design_fir's curve_smooth), taps[F]
+ * float64 without the rounding to float32 of steps 2 and 3.  Like mgx_design_fir a cross-check for tests and tools: it
+ * needs no GPU, takes any power of two from 8 (phase == 1: from 64), and is NOT what the master runs -- there the same
+ * steps happen on the device (csrc/eq_shape_kernels.h).
+ * mgx_master_shaped: mgx_master (reference_dev given, profile_dev NULL) or mgx_master_with_profile (the reverse) with the
+ * FIR designed under `shape`; exactly one of the two is non-null.  shape == NULL is exactly those calls.  The shape is
+ * copied when the call is queued: pipelined calls with different shapes each get their own.  Refusals come before
+ * anything is queued.  mgx_last_fir returns the shaped taps.  mgx_master_with_fir is unaffected: a given FIR is used as
+ * given. */
+typedef struct mgx_eq_shape {
+    double amount;                       /* [0, 2]; 1 = the whole curve */
+    double max_boost_db;                 /* >= 0, or NaN: no cap */
+    double max_cut_db;                   /* >= 0, or NaN: no cap */
+    int32_t phase;                       /* 0 linear, 1 minimum */
+    int32_t reserved;                    /* 0 */
+} mgx_eq_shape;
+int mgx_eq_shape_check(const mgx_config* cfg, const mgx_eq_shape* shape);
+int mgx_shape_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const double* curve_smooth, double* taps);
+int mgx_master_shaped(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
+                      int64_t n_reference, const void* profile_dev, const mgx_config* cfg, const mgx_eq_shape* shape,
+                      float* result_dev, float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
+                      mgx_report* report);
+
 /* match_frequencies.py:104-119 convolve (fftconvolve "same" on mid and side,
  * then ms_to_lr): y = L/R result (n,2), y_mid (n) optional.  taps are host
  * float64 arrays of fft_size entries; `gain` scales both (stages.py:80-88 folded in). */

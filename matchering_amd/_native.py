@@ -149,6 +149,18 @@ class MgxNoiseShaper(ctypes.Structure):
     ]
 
 
+class MgxEqShape(ctypes.Structure):
+    """mgx_eq_shape (include/mgx.h)."""
+
+    _fields_ = [
+        ("amount", ctypes.c_double),
+        ("max_boost_db", ctypes.c_double),
+        ("max_cut_db", ctypes.c_double),
+        ("phase", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
 PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
@@ -189,6 +201,10 @@ SYMBOLS = {
                                    c_double_p, c_int32_p, c_double_p, c_double_p]),
     "mgx_design_fir": (ctypes.c_int, [ctypes.POINTER(MgxConfig), c_double_p, c_double_p, c_double_p,
                                       c_double_p, c_double_p]),
+    "mgx_eq_shape_check": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(MgxEqShape)]),
+    "mgx_shape_fir": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(MgxEqShape), c_double_p, c_double_p]),
+    "mgx_master_shaped": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.POINTER(MgxConfig),
+                                         ctypes.POINTER(MgxEqShape), _VP, _VP, _VP, ctypes.POINTER(MgxReport)]),
     "mgx_convolve": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int32,
                                     ctypes.c_double, _VP, _VP, c_double_p]),
     "mgx_host_alloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_VP)]),

@@ -33,7 +33,9 @@ optional: ``delivery.Delivery``; ``"dither"``: a name -- "lipshitz5" and "wannam
 ``{"coefficients": [...]}`` for a ``delivery.NoiseShaper`` of one's own; ``"limiter"``: ``true`` or the fields of
 ``delivery.TruePeakLimiter``; ``"sample_rate"``: the rate of that file in Hz, converted on the device, default the Config's internal rate); in place of ``"reference"`` a job may name a
 ``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
-list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).
+list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).  A job may carry
+``"eq": {"amount": 0.5, "max_boost_db": 6, "max_cut_db": 6, "phase": "minimum"}`` (every key optional:
+``eq.MatchingEq``), the controls of its matching EQ.
 """
 
 import json
@@ -259,19 +261,24 @@ def lane_device(device_index, lane):
 def _device_worker(device_index, lane, config, needs, master, encodings=None):
     """A callable mastering one (target, reference) array pair on the lane's own device handle.
     ``encodings``: stages.main's (integer PCM renderings straight from the GPU).  ``deliveries`` (per call): a job's
-    ``delivery.DeliveryRequest``, handed to ``main`` where the job has one."""
-    def extra(deliveries):
-        return {"deliveries": deliveries} if deliveries else {}
+    ``delivery.DeliveryRequest``, handed to ``main`` where the job has one; ``eq`` (per call): the job's
+    ``eq.MatchingEq``, likewise."""
+    def extra(deliveries, eq):
+        given = {"deliveries": deliveries} if deliveries else {}
+        if eq is not None:
+            given["eq"] = eq
+        return given
 
     if master is not None:                         # tests inject a stand-in for the GPU
         if encodings is None or not any(encodings):
-            return lambda pair, deliveries=None: master(pair[0], pair[1], config, *needs, **extra(deliveries))
-        return lambda pair, deliveries=None: master(pair[0], pair[1], config, *needs, encodings=encodings, **extra(deliveries))
+            return lambda pair, deliveries=None, eq=None: master(pair[0], pair[1], config, *needs, **extra(deliveries, eq))
+        return lambda pair, deliveries=None, eq=None: master(pair[0], pair[1], config, *needs, encodings=encodings,
+                                                             **extra(deliveries, eq))
     from .stages import main
 
     dev = lane_device(device_index, lane)
-    return lambda pair, deliveries=None: main(pair[0], pair[1], config, *needs, device=dev, encodings=encodings,
-                                              **extra(deliveries))
+    return lambda pair, deliveries=None, eq=None: main(pair[0], pair[1], config, *needs, device=dev, encodings=encodings,
+                                                       **extra(deliveries, eq))
 
 
 def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
@@ -306,7 +313,7 @@ def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
 
 
 def master_album(targets, reference, config=None, rank=None, world_size=None, device_index=None, root=0,
-                 exchange=None, need_default=True, need_no_limiter=False, need_no_limiter_normalized=False):
+                 exchange=None, need_default=True, need_no_limiter=False, need_no_limiter_normalized=False, eq=None):
     """Album mode across the ranks of one node: ONE matching FIR for every track.
 
     Rank ``root`` masters ``targets[0]`` against ``reference`` the ordinary way; the FIR pair it designed
@@ -315,10 +322,15 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     i mod world) with that FIR given (``mgx_master_with_fir``), levels still matched per track.  Returns
     ``{index: triple}`` for this rank's tracks.  ``reference`` may be a ``profile.ReferenceProfile``: the reference
     is then never uploaded or analysed here (``mgx_master_with_profile``).  ``exchange(payload, size)`` must hand rank 0's 128-byte
-    RCCL id to all ranks (bench.Ranks.broadcast_bytes); not needed with one rank."""
+    RCCL id to all ranks (bench.Ranks.broadcast_bytes); not needed with one rank.  ``eq`` (an ``eq.MatchingEq``) shapes
+    the album's one FIR: it applies on the rank that designs it, every other call is given the shaped taps."""
+    from .eq import as_eq
     from .stages import main
 
     config = config if config is not None else Config()
+    eq = as_eq(eq)
+    if eq is not None:
+        eq.check(config)
     r, w, local = rank_and_world(rank, world_size)
     dev = lane_device(local if device_index is None else device_index, 0)
     needs = (need_default, need_no_limiter, need_no_limiter_normalized)
@@ -328,7 +340,7 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     with dev.lock:
         fir = dev.alloc(count * 4)
         if r == root:                                           # the design pass; its result is track 0's
-            first = main(targets[0], reference, config, *needs, device=dev)
+            first = main(targets[0], reference, config, *needs, device=dev, eq=eq)
             taps_ptr, taps = dev.last_fir()
             assert taps == config.fft_size
             designed = dev.download(taps_ptr, (count,))
@@ -569,7 +581,7 @@ def _save_job(job, triple, config, deliveries=None):
 
 
 def process_batch(jobs, config=None, rank=None, world_size=None, device_index=None, lanes=None, io_threads=4,
-                  master=None, share_references=False):
+                  master=None, share_references=False, eq=None):
     """``process`` for a list of jobs, this rank's share only.
 
     ``jobs``: dicts with "target", "reference" (paths) and "results" (list of ``Result``); in place of "reference" a
@@ -580,13 +592,22 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     distinct set is merged once per lane.  Off by default: the profile
     route agrees with the pair route to the project's tolerances, not bit for bit.  Returns
     the indices of the jobs this rank mastered.  The first failing job aborts the rank's batch and
-    its exception is re-raised (after the jobs already in flight have finished)."""
+    its exception is re-raised (after the jobs already in flight have finished).  ``eq``: the ``eq.MatchingEq`` of every
+    job that has no "eq" of its own (an ``eq.MatchingEq`` or the JSON object of one); what the library refuses is a
+    ValueError before a file is read."""
+    from .eq import as_eq
+
     config = config if config is not None else Config()
     r, w, local = rank_and_world(rank, world_size)
     mine = shard(jobs, r, w)
+    eq = as_eq(eq)
+    eqs = {}
     for i in mine:
         if not jobs[i].get("results"):
             raise RuntimeError("The result list is empty")
+        eqs[i] = as_eq(jobs[i]["eq"]) if jobs[i].get("eq") is not None else eq
+        if eqs[i] is not None:
+            eqs[i].check(config)
         # (a delivery rate the device converter refuses is a ValueError here, before a file is read)
         from .delivery import DeliveryRequest
 
@@ -657,9 +678,10 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                     workers[key] = _device_worker(device_index, lane, config, needs, master, key[1])
                 if later is not None:
                     target, reference = _on_the_lane(target, reference, later, device_index, lane, config, master)
+                shaped = {} if eqs[index] is None else {"eq": eqs[index]}
                 if not deliveries:
-                    return workers[key]((target, reference))
-                return _WithDeliveries(workers[key]((target, reference), deliveries), deliveries)
+                    return workers[key]((target, reference), **shaped)
+                return _WithDeliveries(workers[key]((target, reference), deliveries, **shaped), deliveries)
             return run
 
         if lanes is None:
@@ -714,6 +736,10 @@ def jobs_from_json(path):
                           delivery=None if r.get("delivery") is None else Delivery.from_json(r["delivery"]))
                    for r in item["results"]]
         job = {"target": item["target"], "results": results}
+        if item.get("eq") is not None:
+            from .eq import MatchingEq
+
+            job["eq"] = MatchingEq.from_json(item["eq"])
         for key in REFERENCE_KEYS:
             if item.get(key) is not None:
                 job[key] = item[key]

@@ -190,11 +190,18 @@ def _write_results(results, renderings, sample_rate, deliveries=None):
 
 
 def process(target: str, reference: str, results: list, config: Config = None,
-            preview_target: Result = None, preview_result: Result = None, loudness=None):
+            preview_target: Result = None, preview_result: Result = None, loudness=None, eq=None):
     # (``loudness``: no counterpart in the reference -- a callable that receives (name, loudness.Loudness) for "target",
     # for "reference" when its audio was loaded, and for each rendering the results need ("result", "result_no_limiter",
-    # "result_no_limiter_normalized"), measured on the frames in HBM; None: nothing is measured, nothing else changes)
+    # "result_no_limiter_normalized"), measured on the frames in HBM; None: nothing is measured, nothing else changes.
+    # ``eq``: an eq.MatchingEq -- how much of the matching curve is applied, its boost and cut caps, the phase of the FIR;
+    # None: the reference's FIR.  What the library refuses is a ValueError before a file is read.)
+    from .eq import as_eq
+
     config = Config() if config is None else config
+    eq = as_eq(eq)
+    if eq is not None:
+        eq.check(config)
     debug("matchering_amd: the MI355X path behind the API of https://github.com/sergree/matchering")
     debug_line()
     info(Code.INFO_LOADING)
@@ -232,6 +239,8 @@ def process(target: str, reference: str, results: list, config: Config = None,
         extra["loudness"] = loudness
     if deliveries:
         extra["deliveries"] = deliveries
+    if eq is not None:
+        extra["eq"] = eq
     renderings = main(resident[0] if resident[0] is not None else target_audio,
                       resident[1] if resident[1] is not None else reference_audio,
                       config, *_wanted_renderings(ordinary), encodings=encodings, **extra)   # (releases the resident frames)

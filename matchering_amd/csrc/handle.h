@@ -84,6 +84,10 @@ struct PlanDev {
 static std::mutex g_plan_mu;
 static std::map<std::pair<int, const FirPlanHost*>, PlanDev> g_plan_dev;
 
+// exp(2 pi i j / N), j < N, float64: the twiddles of the minimum-phase chain (eq_shape_kernels.h), one table per
+// (device, N) for the whole process, made on first use and kept like the plans above
+static std::map<std::pair<int, int>, double2*> g_minphase_twiddles;
+
 // Limiter launches of one device never run side by side.  k_limit deals its chunks by workgroup number (no atomic
 // ticket): a chunk waits for words of lower-numbered chunks only, and every XCD's dispatcher hands out its share of a
 // grid in order, so within ONE launch the lowest unfinished chunk is always resident.  Two limiter launches resident
@@ -115,6 +119,7 @@ struct CallContext {
     TrackWork track[2];
     DevBuf fir_scratch, scalars, taps, filt, cstate;
     DevBuf fir_robust;                      // lowess_it > 0: robustness weights and residuals, [2][2][nlog]
+    DevBuf eq_work;                         // a minimum-phase matching EQ: the chain's two planes and maxima (eq_shape_kernels.h)
     int last_taps = 0;
 };
 
@@ -180,6 +185,8 @@ struct mgx_handle {
         mgx_config cfg;
         LimiterParams lp;                   // derived from cfg when out[0] (the limited result) is wanted
         float* out[3] = {nullptr, nullptr, nullptr};
+        bool shaped = false;                // mgx_master_shaped with a shape: `shape` is the call's own copy
+        mgx_eq_shape shape = {};
     } last_call;
     bool avoid_tail = false;                // sticky after such a report: rounds 1..K-1 as one launch each (MGX_NO_TAIL=1: always)
     bool requeued = false;                  // the last check_device_error queued the call again

@@ -672,6 +672,18 @@ int mgx_master_with_fir(mgx_handle* h, const float* target_dev, int64_t n_target
                        result_no_limiter_dev, result_no_limiter_normalized_dev, report);
 }
 
+// the matching EQ's controls (mgx_eq_shape_check, mgx_shape_fir: mgx_policy.cpp)
+int mgx_master_shaped(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
+                      int64_t n_reference, const void* profile_dev, const mgx_config* cfg, const mgx_eq_shape* shape,
+                      float* result_dev, float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
+                      mgx_report* report) {
+    if ((reference_dev != nullptr) == (profile_dev != nullptr))
+        return fail(MGX_ERR_ARGUMENT, "mgx_master_shaped takes a reference track or a reference profile, exactly one of them");
+    return master_impl(h, target_dev, n_target, reference_dev, profile_dev ? 0 : n_reference,
+                       (const mgx_profile_header*)profile_dev, cfg, nullptr, result_dev, result_no_limiter_dev,
+                       result_no_limiter_normalized_dev, report, shape);
+}
+
 // ---- reference profiles (mgx_profile_bytes: mgx_policy.cpp) --------------------
 int mgx_reference_profile(mgx_handle* h, const float* reference_dev, int64_t n_reference, const mgx_config* cfg,
                           void* profile_dev) {

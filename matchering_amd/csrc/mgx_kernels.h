@@ -590,3 +590,4 @@ __global__ __launch_bounds__(Fft2<LOG2H>::T, analysis_waves_per_simd<LOG2H>()) v
 #include "io_kernels.h"
 #include "limiter_kernels.h"
 #include "profile_kernels.h"       // (off the pair route's chain: last, so that it moves none of the kernels above)
+#include "eq_shape_kernels.h"      // (likewise: only a call with an mgx_eq_shape launches them)

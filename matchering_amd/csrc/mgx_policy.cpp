@@ -4,8 +4,12 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <complex>
 #include <cstring>
+#include <memory>
+#include <vector>
 
+#include "fir_plan.h"
 #include "host_params.h"
 
 namespace mgx {
@@ -203,6 +207,35 @@ static int delivery_room(const mgx_delivery* delivery, const mgx_noise_shaper* s
     return 0;
 }
 
+bool eq_shape_curve_stage(const mgx_eq_shape* shape) {
+    return shape && (shape->amount != 1.0 || !std::isnan(shape->max_boost_db) || !std::isnan(shape->max_cut_db));
+}
+bool eq_shape_minimum_phase(const mgx_eq_shape* shape) { return shape && shape->phase == 1; }
+
+// in-place radix-2 complex transform of n = 2^k points for mgx_shape_fir: sign -1 forward, +1 inverse, unnormalised.
+// Every twiddle is its own cos / sin of an exactly representable fraction of the circle.
+static void shape_fft(std::vector<std::complex<double>>& a, int sign) {
+    const int n = (int)a.size();
+    for (int i = 1, j = 0; i < n; ++i) {
+        int bit = n >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) std::swap(a[i], a[j]);
+    }
+    const double pi = 3.14159265358979323846;
+    std::vector<std::complex<double>> w(n / 2);
+    for (int k = 0; k < n / 2; ++k) w[k] = std::complex<double>(std::cos(2.0 * pi * k / n), sign * std::sin(2.0 * pi * k / n));
+    for (int len = 2; len <= n; len <<= 1) {
+        const int half = len / 2, stride = n / len;
+        for (int i = 0; i < n; i += len)
+            for (int k = 0; k < half; ++k) {
+                const std::complex<double> u = a[i + k], v = a[i + k + half] * w[(size_t)k * stride];
+                a[i + k] = u + v;
+                a[i + k + half] = u - v;
+            }
+    }
+}
+
 }  // namespace mgx
 
 using namespace mgx;
@@ -246,6 +279,80 @@ int mgx_design_fir(const mgx_config* cfg, const double* avg_target, const double
     MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
     if (cfg->lowess_it < 0 || cfg->lowess_it > 64) return fail(MGX_ERR_ARGUMENT, "lowess_it outside [0, 64]");
     design_fir(avg_target, avg_reference, fir_design_params(*cfg), taps, curve_raw, curve_smooth);
+    return 0;
+}
+
+// ---- matching EQ controls ---------------------------------------------------------
+// the values of a shape, whatever the size
+static int eq_shape_values(const mgx_eq_shape* shape) {
+    if (!std::isfinite(shape->amount) || shape->amount < 0.0 || shape->amount > 2.0)
+        return fail(MGX_ERR_ARGUMENT, "amount: outside [0, 2]");
+    if (!std::isnan(shape->max_boost_db) && (std::isinf(shape->max_boost_db) || shape->max_boost_db < 0.0))
+        return fail(MGX_ERR_ARGUMENT, "max_boost_db: must be finite and not negative (NaN: no cap)");
+    if (!std::isnan(shape->max_cut_db) && (std::isinf(shape->max_cut_db) || shape->max_cut_db < 0.0))
+        return fail(MGX_ERR_ARGUMENT, "max_cut_db: must be finite and not negative (NaN: no cap)");
+    if (shape->phase != 0 && shape->phase != 1) return fail(MGX_ERR_ARGUMENT, "phase: 0 (linear) or 1 (minimum)");
+    if (shape->reserved != 0) return fail(MGX_ERR_ARGUMENT, "reserved: must be 0");
+    return 0;
+}
+
+int mgx_eq_shape_check(const mgx_config* cfg, const mgx_eq_shape* shape) {
+    if (!cfg || !shape) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(eq_shape_values(shape));
+    if (shape->phase == 1 && (cfg->fft_size < EQ_MINPHASE_FFT_MIN || cfg->fft_size > EQ_MINPHASE_FFT_MAX))
+        return fail(MGX_ERR_UNSUPPORTED, "a minimum-phase matching EQ is implemented for fft_size " + std::to_string(EQ_MINPHASE_FFT_MIN) +
+                                         " to " + std::to_string(EQ_MINPHASE_FFT_MAX) + ", not " + std::to_string(cfg->fft_size));
+    return 0;
+}
+
+int mgx_shape_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const double* curve_smooth, double* taps) {
+    if (!cfg || !shape || !curve_smooth || !taps) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const char* const refusal = "bad fft_size";                 // (no upper bound, as for mgx_design_fir)
+    MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
+    MGX_TRY(eq_shape_values(shape));                            // (the upper end of the size range is the device's)
+    const int f = cfg->fft_size, half = f / 2;
+    if (shape->phase == 1 && f < EQ_MINPHASE_FFT_MIN)
+        return fail(MGX_ERR_UNSUPPORTED, "a minimum-phase matching EQ needs fft_size 64 or more, not " + std::to_string(f));
+    // 1. shape
+    std::vector<double> s(curve_smooth, curve_smooth + half + 1);
+    if (eq_shape_curve_stage(shape)) {
+        s[0] = 0.0;
+        for (int k = 1; k <= half; ++k) {
+            double d = shape->amount * (20.0 * std::log10(std::max(s[k], cfg->min_value)));
+            if (!std::isnan(shape->max_boost_db)) d = std::min(d, shape->max_boost_db);
+            if (!std::isnan(shape->max_cut_db)) d = std::max(d, -shape->max_cut_db);
+            s[k] = std::pow(10.0, d / 20.0);
+        }
+    }
+    // 2. linear-phase taps: the design's own synthesis
+    {
+        const std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(fir_design_params(*cfg));
+        const FirPlanView pl = plan->view(plan->blob());
+        for (int tid = 0; tid < FirDesign::T; ++tid) FirDesign::phase_taps(tid, pl, s.data(), nullptr, taps);
+    }
+    if (shape->phase != 1) return 0;
+    // 3. minimum phase by the folded cepstrum on N = 4F points
+    const int n = 4 * f;
+    std::vector<std::complex<double>> x(n);
+    for (int k = 0; k < f; ++k) x[k] = taps[k];
+    shape_fft(x, -1);
+    double top = 0.0;
+    for (int m = 0; m < n; ++m) top = std::max(top, std::abs(x[m]));
+    for (int m = 0; m < n; ++m) x[m] = std::log(std::max(std::abs(x[m]), 1e-9 * top));
+    shape_fft(x, +1);
+    for (int m = 0; m < n; ++m) {
+        const double c = x[m].real() / n;
+        x[m] = m == 0 || m == n / 2 ? c : (m < n / 2 ? 2.0 * c : 0.0);
+    }
+    shape_fft(x, -1);
+    for (int m = 0; m < n; ++m) x[m] = std::exp(x[m]);
+    shape_fft(x, +1);
+    const double pi = 3.14159265358979323846;
+    for (int j = 0; j < half; ++j) {
+        const double taper = j < f / 4 ? 1.0 : 0.5 * (1.0 + std::cos(pi * (j - f / 4) / (f / 4)));
+        taps[j] = 0.0;
+        taps[half + j] = x[j].real() / n * taper;
+    }
     return 0;
 }
 

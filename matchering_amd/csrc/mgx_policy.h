@@ -1,7 +1,7 @@
 // The part of libmgx.so that touches no device (mgx_policy.cpp): the calling thread's error text, the validation of a
 // Config, the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
 // mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
-// mgx_noise_shaper_preset, mgx_profile_bytes --
+// mgx_noise_shaper_preset, mgx_profile_bytes, mgx_eq_shape_check, mgx_shape_fir --
 // and what the device entry points settle from their numbers alone before they touch a handle.
 // No HIP here: g++ compiles the unit by itself (tests/emu/emu_policy_driver.cpp runs it under the sanitizers), and
 // mgx.hip uses what is declared below.
@@ -53,5 +53,11 @@ constexpr double TP_LIMIT_RELEASE_MAX = 4194304.0;             // 2^22 frames
 int tp_limit_check(int64_t n, double pre_gain, double ceiling, int32_t lookahead, double release);
 int profile_merge_check(const void* const* profiles_dev, const int32_t* weights, int32_t count, const mgx_config* cfg,
                         const void* profile_dev);
+// matching EQ controls (mgx_eq_shape): the fft_size range of the minimum-phase chain (eq_shape_kernels.h: N = 4F points
+// per channel through the call's scratch), and what a shape asks of the design -- false for NULL and for a shape that
+// changes nothing, which then costs no launch
+constexpr int EQ_MINPHASE_FFT_MIN = 64, EQ_MINPHASE_FFT_MAX = 16384;
+bool eq_shape_curve_stage(const mgx_eq_shape* shape);          // amount != 1 or a cap: k_eq_shape runs
+bool eq_shape_minimum_phase(const mgx_eq_shape* shape);
 
 }  // namespace mgx

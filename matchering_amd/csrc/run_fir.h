@@ -172,10 +172,51 @@ static int run_pair_curve(mgx_handle* h, const mgx_config* cfg, const FirPlanVie
     return 0;
 }
 
+// The designed taps of `cx` -> their minimum-phase form, in place (eq_shape_kernels.h): four transforms of N = 4F float64
+// points per channel, a sub-transform launch and a combine launch each.  fft from 64 to 16384 (mgx_eq_shape_check).
+static int run_minimum_phase(mgx_handle* h, CallContext& cx, int fft) {
+    MinPhaseArgs a;
+    a.fft = fft;
+    a.n = fft * MINPHASE_OVERSAMPLE;
+    minphase_geometry(fft, a.log2m, a.r);
+    {
+        std::lock_guard<std::mutex> lock(g_plan_mu);
+        double2*& table = g_minphase_twiddles[std::make_pair(h->device, a.n)];
+        if (!table) {
+            std::vector<double2> host(a.n);
+            const double pi = 3.14159265358979323846;
+            for (int j = 0; j < a.n; ++j) host[j] = make_double2(std::cos(2.0 * pi * j / a.n), std::sin(2.0 * pi * j / a.n));
+            DevBuf tmp;
+            HIP_TRY(hipMalloc(&tmp.p, host.size() * sizeof(double2)));
+            HIP_TRY(hipMemcpy(tmp.p, host.data(), host.size() * sizeof(double2), hipMemcpyHostToDevice));
+            table = (double2*)tmp.p;
+            tmp.p = nullptr;
+        }
+        a.tw = table;
+    }
+    MGX_TRY(ensure(h, cx.eq_work, minphase_work_bytes(fft)));
+    a.taps = (float*)cx.taps.p;
+    a.a = (double2*)cx.eq_work.p;
+    a.b = a.a + (size_t)2 * a.n;
+    a.hmax = (unsigned long long*)(a.b + (size_t)2 * a.n);
+    const int threads = minphase_threads(a.log2m);
+    const size_t lds = minphase_lds_bytes(a.log2m);
+    MGX_TRY(allow_lds(k_minphase_sub, lds));
+    for (int step = 0; step < 4; ++step) {
+        hipLaunchKernelGGL(k_minphase_sub, dim3(a.r, 2), dim3(threads), lds, h->fq, a, step);
+        hipLaunchKernelGGL(k_minphase_combine, dim3((minphase_combine_count(a, step) + 255) / 256, 2), dim3(256), 0, h->fq, a,
+                           step);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // fir_given: a FIR pair to use instead of the designed one (album mode), or null.  profile: the reference as a profile
 // (then `rw` is not looked at), or null
+// shape: the matching EQ's controls (include/mgx.h, mgx_eq_shape; checked by the caller), or null
 static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const TrackWork& rw,
-                          const float* fir_given, const mgx_profile_header* profile = nullptr) {
+                          const float* fir_given, const mgx_profile_header* profile = nullptr,
+                          const mgx_eq_shape* shape = nullptr) {
     CallContext& cx = context(h);
     std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(fir_design_params(*cfg));
     // no operator when LOWESS is not linear (robustness passes): the chain runs on the curve itself.  Otherwise the
@@ -254,6 +295,10 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
         hipLaunchKernelGGL(k_fir_matvec, dim3(pl.bins), dim3(256), 0, h->fq, pl, (const double*)pd.M,
                            (const int2*)pd.band, (const double*)raw, scratch);
     }
+    // the matching EQ's shape stage, in place on the two smooth planes: launched only where it changes the curve
+    if (eq_shape_curve_stage(shape))
+        hipLaunchKernelGGL(k_eq_shape, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->fq, pl, scratch,
+                           EqShapeArgs{shape->amount, shape->max_boost_db, shape->max_cut_db, cfg->min_value});
     if (pl.fft < 64) {                                          // 8 .. 32 taps: the plain cosine sum, one thread per tap
         hipLaunchKernelGGL(k_fir_taps_direct, dim3(2), dim3(1024), 0, h->fq, pl, (const double*)scratch, (float*)cx.taps.p);
         HIP_TRY(hipGetLastError());
@@ -289,6 +334,7 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
                            pl, (const double*)scratch, (float*)cx.taps.p);
     }
     HIP_TRY(hipGetLastError());
+    if (eq_shape_minimum_phase(shape)) MGX_TRY(run_minimum_phase(h, cx, cfg->fft_size));
     cx.last_taps = cfg->fft_size;
     return 0;
 }

@@ -595,20 +595,26 @@ class Device:
                 block.release()
 
     def master(self, target, n_target, reference, n_reference, native_config, result=None,
-               result_no_limiter=None, result_no_limiter_normalized=None, want_report=True, fir=None, profile=None):
+               result_no_limiter=None, result_no_limiter_normalized=None, want_report=True, fir=None, profile=None,
+               eq=None):
         """``mgx_master`` on device buffers.  Outputs are DeviceBuffers or None.  ``fir`` (a DeviceBuffer
         holding [2][fft_size] float32) replaces the designed matching FIR: ``mgx_master_with_fir``.  ``profile``
         (a DeviceBuffer holding a reference profile) stands for the reference, which is then None:
-        ``mgx_master_with_profile``."""
+        ``mgx_master_with_profile``.  ``eq`` (an ``eq.MatchingEq``) shapes the FIR that is designed:
+        ``mgx_master_shaped``, on either route; a given ``fir`` is used as given, whatever ``eq`` says."""
         report = MgxReport() if want_report else None
 
         def p(b):
             return ctypes.c_void_p(b.ptr) if b is not None else None
 
         rep = ctypes.byref(report) if report is not None else None
-        if profile is not None:
-            if reference is not None:
-                raise ValueError("master: a reference track or a reference profile, not both")
+        if profile is not None and reference is not None:
+            raise ValueError("master: a reference track or a reference profile, not both")
+        if eq is not None and fir is None:
+            check(library().mgx_master_shaped(
+                self.handle, p(target), n_target, p(reference), n_reference, p(profile), ctypes.byref(native_config),
+                ctypes.byref(eq.to_native()), p(result), p(result_no_limiter), p(result_no_limiter_normalized), rep))
+        elif profile is not None:
             check(library().mgx_master_with_profile(
                 self.handle, p(target), n_target, p(profile), ctypes.byref(native_config), p(fir),
                 p(result), p(result_no_limiter), p(result_no_limiter_normalized), rep))

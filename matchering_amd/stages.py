@@ -77,7 +77,7 @@ def _limited(dev, rendering, n, rate, delivery, bits, measured):
 
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
-         encodings=None, preview=None, loudness=None, deliveries=None):
+         encodings=None, preview=None, loudness=None, deliveries=None, eq=None):
     # (``device``: the handle to run on, default the process-wide one; ``fir``: a DeviceBuffer with a
     # matching FIR to apply instead of designing one -- batch.master_album; ``encodings``: per output,
     # None for float32 frames or "PCM_16" / "PCM_24" / "PCM_32" for the integer samples a file of that
@@ -97,7 +97,14 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # delivery that carries a limiter and whose ceiling binds is limited first (mgx_tp_limit, mgx_delivery_limit_step).  A
     # noise-shaped delivery takes the _shaped policy and mgx_deliver_shaped in their place.  A
     # delivery at another ``sample_rate`` than the internal one is made from the rendering converted to that rate in HBM
-    # (mgx_convert_rate) and measured there; the renderings returned, the previews and the other callbacks do not change.)
+    # (mgx_convert_rate) and measured there; the renderings returned, the previews and the other callbacks do not change.
+    # ``eq``: an eq.MatchingEq (or its JSON object) -- how much of the matching curve is applied, its boost and cut
+    # caps, the FIR's phase (mgx_master_shaped); None: the reference's FIR.  A given ``fir`` is used as given.)
+    from .eq import as_eq
+
+    eq = as_eq(eq)
+    if eq is not None:
+        eq.check(config)                                     # (ValueError before anything reaches the GPU)
     dev = device if device is not None else default_device()
     target = _as_frames(target, "target")
     profile = reference if _is_profile(reference) else None
@@ -128,6 +135,8 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
         outs = [dev.alloc(n * 8) if need or extra else None for need, extra in zip(returned, cut)]
         try:
             route = {} if p_dev is None else {"profile": p_dev}
+            if eq is not None:
+                route["eq"] = eq
             report = dev.master(t_dev, n, r_dev, nr, native, *outs, fir=fir, **route)
             debug(f"target: {report.target_divisions} pieces of {report.target_piece} frames, "
                   f"{report.target_loud_count} of them loud; reference: {report.reference_divisions} pieces of "
@@ -138,6 +147,8 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
             debug(f"level match: {to_db(report.rms_coefficient)} on the target")
             debug_line()
             info(Code.INFO_MATCHING_FREQS)
+            if eq is not None and fir is None:
+                debug(eq.describe())
             debug_line()
             info(Code.INFO_CORRECTING_LEVELS)
             kept = len(report.correction_coefficients)               # (mgx_report keeps the first 16 coefficients)
