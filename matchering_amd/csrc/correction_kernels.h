@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_clipped_sumsq(const float* mid, long lo
 // workgroup also derives the peak / limiter early-out / normalisation scalars (k_finalize_scalars).
 // Band bookkeeping of one workgroup's chunk (k_correction_round).  Every correction coefficient is
 // close to 1 (it is the ratio of two loudness estimates of nearly the same signal), so the
-// accumulated gain g stays inside [BAND_G_LO, BAND_G_HI].  For such g a sample with
+// accumulated gain g of an ordinary pair stays inside [BAND_G_LO, BAND_G_HI].  For such g a sample with
 // |m| <= 1/BAND_G_HI is never clipped (contributes g^2 m^2), one with |m| > 1/BAND_G_LO always is
 // (contributes 1), and only the few samples in between -- the band -- need to be looked at again.
 // Round 0 streams the whole mid plane once, evaluates its own sum directly AND leaves
@@ -448,8 +448,11 @@ __global__ __launch_bounds__(256) void k_correction_round(RoundArgs a) {
 // takes round 0's decision while the others copy their lists) polls the words, one lane per word, decides
 // with one wave and publishes the new gain the same way -> everybody polls it (one lane, bounded) and goes on.  Every wait
 // is bounded and raises the handle's error word.  A gain outside [BAND_G_LO, BAND_G_HI] makes a
-// workgroup stream its part of the mid plane instead (slow with so few workgroups, and never seen:
-// coefficients are ratios of two loudness estimates of nearly the same signal).
+// workgroup stream its part of the mid plane instead (slow with so few workgroups).  Ordinary pairs stay inside
+// the band -- coefficients are ratios of two loudness estimates of nearly the same signal -- but hard material does
+// leave it: a sparse or narrow-band target against a dense reference goes below BAND_G_LO from round 1 on
+// (running gains 0.35 .. 0.07, 0.61 .. 0.54, 0.52), an ordinary target against a hard-clipped reference crosses
+// BAND_G_HI in the middle of the tail, a click train reaches 35 (tests/test_gpu_band_exits.py holds each).
 // Phase stamps of this kernel and of round 0's last workgroup: profiles/r03_z_correction_phases.txt
 // (-DMGX_TAIL_TRACE, tools/tail_trace.py).
 #ifdef MGX_TEST_TAIL_MAX_SPINS                             // tests/test_device_errors.py: a tail that gives up quickly

@@ -1,8 +1,39 @@
-// The small streaming kernels around the master chain (device only): the scaled outputs (k_scale_outputs), window
-// energies and the preview cut, per-block frame peaks, PCM decode / encode at the file boundary, and the peak count
-// (k_peak_max, k_peak_count).
+// The small streaming kernels around the master chain: the scaled outputs (k_scale_outputs), window energies and the
+// preview cut, per-block frame peaks, PCM decode / encode at the file boundary, and the peak count (k_peak_max,
+// k_peak_count).  The kernels are device only.  The launch geometry of the grid-stride ones stands first and compiles
+// under a plain host compiler as well (-DMGX_HOST_EMU: tests/emu/emu.cpp exports it, so that the lengths at which
+// the tests make a grid wrap follow these numbers).
 #pragma once
 
+#include "mgx_hd.h"
+
+namespace mgx {
+
+constexpr int PCM_GRID_MAX = 8192;              // workgroups of k_pcm_decode / k_pcm_encode: longer files wrap (grid-stride)
+constexpr int PEAK_GRID_MAX = 4096;             // ... of k_peak_max / k_peak_count
+constexpr int PREVIEW_CUT_GRID_MAX = 4096;      // ... of k_preview_cut
+constexpr int WINDOW_ENERGY_ROWS_MAX = 65535;   // windows of one k_window_energy launch (a grid's y extent is 16 bits)
+constexpr int WINDOW_ENERGY_CHUNK_FRAMES = 16384, WINDOW_ENERGY_CHUNKS_MAX = 64;    // a window's workgroups: size / 16384, 1 .. 64
+
+// four samples per thread, and one workgroup more for the ragged end
+inline long long quad_grid(long long samples, int cap) {
+    const long long blocks = (samples / 4 + 255) / 256 + 1;
+    return blocks < cap ? blocks : cap;
+}
+inline long long pcm_grid(long long samples) { return quad_grid(samples, PCM_GRID_MAX); }
+inline long long peak_grid(long long samples) { return quad_grid(samples, PEAK_GRID_MAX); }
+inline long long preview_cut_grid(long long size) {
+    const long long blocks = (size + 255) / 256;
+    return blocks < PREVIEW_CUT_GRID_MAX ? blocks : PREVIEW_CUT_GRID_MAX;
+}
+inline int window_energy_chunks(long long size) {
+    const long long chunks = size / WINDOW_ENERGY_CHUNK_FRAMES;
+    return (int)(chunks < 1 ? 1 : (chunks > WINDOW_ENERGY_CHUNKS_MAX ? WINDOW_ENERGY_CHUNKS_MAX : chunks));
+}
+
+}  // namespace mgx
+
+#if defined(__HIPCC__) && !defined(MGX_HOST_EMU)
 #include "wave_util.h"
 
 namespace mgx {
@@ -225,3 +256,4 @@ __global__ __launch_bounds__(256) void k_peak_count(const float* x, long long sa
 }
 
 }  // namespace mgx
+#endif

@@ -378,7 +378,7 @@ int mgx_peak_count(mgx_handle* h, const float* x_dev, int64_t samples, double* p
     unsigned long long* words = (unsigned long long*)h->peak_words.p;
     HIP_TRY(hipMemsetAsync(words, 0, 16, h->stream));
     if (samples > 0) {
-        const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 4096);
+        const unsigned grid = (unsigned)peak_grid(samples);
         hipLaunchKernelGGL(k_peak_max, dim3(grid), dim3(256), 0, h->stream, x_dev, (long long)samples, words);
         hipLaunchKernelGGL(k_peak_count, dim3(grid), dim3(256), 0, h->stream, x_dev, (long long)samples, words);
         HIP_TRY(hipGetLastError());
@@ -453,12 +453,12 @@ int mgx_window_energy(mgx_handle* h, const float* x_dev, int64_t n, int64_t size
     const int64_t windows = (n - size) / step + 1;
     *count = windows;
     if (windows > capacity) return fail(MGX_ERR_ARGUMENT, "energy array too small for the number of windows");
-    const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(64, size / 16384));
+    const int chunks = window_energy_chunks(size);
     const size_t bytes = (size_t)windows * chunks * sizeof(double);
     MGX_TRY(ensure(h, h->partial, bytes));
     MGX_TRY(ensure_pinned(h, std::max(bytes, (size_t)1 << 16)));
-    for (int64_t w0 = 0; w0 < windows; w0 += 65535) {          // (a grid's y extent is 16 bits; the reference has no limit)
-        const unsigned rows = (unsigned)std::min<int64_t>(65535, windows - w0);
+    for (int64_t w0 = 0; w0 < windows; w0 += WINDOW_ENERGY_ROWS_MAX) {      // (the reference has no limit)
+        const unsigned rows = (unsigned)std::min<int64_t>(WINDOW_ENERGY_ROWS_MAX, windows - w0);
         hipLaunchKernelGGL(k_window_energy, dim3(chunks, rows), dim3(256), 0, h->stream, (const float2*)x_dev,
                            (long long)size, (long long)step, chunks, (double*)h->partial.p, (long long)w0);
     }
@@ -475,7 +475,7 @@ int mgx_preview_cut(mgx_handle* h, const float* x_dev, int64_t n, int64_t begin,
     if (!h || !x_dev || !out_dev || begin < 0 || size < 1 || begin + size > n || fade < 0 || fade > size)
         return fail(MGX_ERR_ARGUMENT, "bad preview cut arguments");
     MGX_TRY(open_main(h));
-    const unsigned grid = (unsigned)std::min<int64_t>((size + 255) / 256, 4096);
+    const unsigned grid = (unsigned)preview_cut_grid(size);
     hipLaunchKernelGGL(k_preview_cut, dim3(grid), dim3(256), 0, h->stream, (const float2*)x_dev, (long long)begin,
                        (long long)size, (long long)fade, clip_limit, (float2*)out_dev);
     HIP_TRY(hipGetLastError());
@@ -487,7 +487,7 @@ int mgx_pcm_decode(mgx_handle* h, const void* pcm_dev, int64_t samples, int32_t 
     if (bits != 16 && bits != 24 && bits != 32) return fail(MGX_ERR_ARGUMENT, "PCM width must be 16, 24 or 32 bits");
     if (samples <= 0) return 0;
     MGX_TRY(open_main(h));
-    const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 8192);
+    const unsigned grid = (unsigned)pcm_grid(samples);
     hipLaunchKernelGGL(k_pcm_decode, dim3(grid), dim3(256), 0, h->stream, pcm_dev, (long long)samples, bits, out_dev);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -498,7 +498,7 @@ int mgx_pcm_encode(mgx_handle* h, const float* x_dev, int64_t samples, int32_t b
     if (bits != 16 && bits != 24 && bits != 32) return fail(MGX_ERR_ARGUMENT, "PCM width must be 16, 24 or 32 bits");
     if (samples <= 0) return 0;
     MGX_TRY(open_main(h));
-    const unsigned grid = (unsigned)std::min<long long>((samples / 4 + 255) / 256 + 1, 8192);
+    const unsigned grid = (unsigned)pcm_grid(samples);
     hipLaunchKernelGGL(k_pcm_encode, dim3(grid), dim3(256), 0, h->stream, x_dev, (long long)samples, bits, pcm_dev);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -20,6 +20,7 @@
 #include "../../matchering_amd/csrc/conv_wide_kernel.h"
 #include "../../matchering_amd/csrc/fir_design.h"
 #include "../../matchering_amd/csrc/host_params.h"
+#include "../../matchering_amd/csrc/io_kernels.h"
 #include "../../matchering_amd/csrc/fir_plan.h"
 
 using namespace mgx;
@@ -992,4 +993,18 @@ extern "C" int emu_limiter_geometry(const mgx_config* cfg, int* threads, int* co
     if (gr) *gr = lp.geo.gr;
     if (general) *general = lp.general;
     return 0;
+}
+
+// The grids libmgx launches for its small streaming kernels (io_kernels.h), by the functions the library itself calls:
+// 0 k_pcm_decode / k_pcm_encode (samples), 1 k_peak_max / k_peak_count (samples), 2 k_preview_cut (frames),
+// 3 the workgroups of one window of k_window_energy (frames of the window), 4 the windows of one launch of it.
+extern "C" long long emu_io_grid(int which, long long items) {
+    switch (which) {
+    case 0: return pcm_grid(items);
+    case 1: return peak_grid(items);
+    case 2: return preview_cut_grid(items);
+    case 3: return window_energy_chunks(items);
+    case 4: return WINDOW_ENERGY_ROWS_MAX;
+    }
+    return -1;
 }

@@ -1,7 +1,8 @@
 """The matching EQ's device phase functions (csrc/eq_shape_kernels.h) under the host emulation (tests/emu/emu_eq_shape.cpp)
 against tests/eq_oracle.py, without a GPU: the sizes at which the minimum-phase chain changes its route -- 1024 taps, the
 largest at which a channel's transform is one workgroup; 2048, the smallest that is split -- the smallest size, 64, and
-16384, where sixteen workgroups share a transform.
+16384, where sixteen workgroups share a transform; 128 and 512, whose transforms have an odd log2 (the radix-2 stage in
+front of the radix-4 passes), and 8192, eight workgroups.
 """
 
 import numpy as np
@@ -22,7 +23,7 @@ def curve(fft, seed):
 def test_route_boundaries():
     """One workgroup per channel and transform up to N = 4096 points, then 4096-point sub-transforms; the LDS of a
     workgroup stays under the 150 KB a launch may ask for, the scratch is two [2][N] double2 planes and two maxima."""
-    want = {64: (8, 1), 256: (10, 1), 512: (11, 1), 1024: (12, 1), 2048: (12, 2), 4096: (12, 4), 16384: (12, 16)}
+    want = {64: (8, 1), 128: (9, 1), 256: (10, 1), 512: (11, 1), 1024: (12, 1), 2048: (12, 2), 4096: (12, 4), 8192: (12, 8), 16384: (12, 16)}
     for fft, (log2m, r) in want.items():
         g = eq_shape_emu.geometry(fft)
         assert (g["log2m"], g["r"]) == (log2m, r)
@@ -31,7 +32,7 @@ def test_route_boundaries():
         assert g["work_bytes"] == 4 * (4 * fft) * 16 + 16
 
 
-@pytest.mark.parametrize("fft", [64, 512, 1024, 2048, 16384])
+@pytest.mark.parametrize("fft", [64, 128, 512, 1024, 2048, 8192, 16384])
 def test_emulated_chain_matches_the_oracle(fft):
     """float32 linear taps in, float32 minimum-phase taps out: <= 2e-7 of the peak against eq_oracle's float64 chain on the
     same float32 input (one float32 rounding, 6e-8, with margin), both channels; zero before F/2."""

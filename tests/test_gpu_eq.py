@@ -3,7 +3,13 @@
 Pairs of 2-3 s from matchering_amd.synth.make_pair, the generator of the golden cases.  The oracle of a size runs once
 per module.  Sizes: 64 (the smallest the minimum-phase chain takes), 1024 (the largest at which a channel's transform is
 one workgroup), 2048 (the smallest that is split), 4096 (the default; the cosine-sum tap synthesis) and 16384 (BASELINE
-config #5; the transform tap synthesis, the factored curve route).
+config #5; the transform tap synthesis, the factored curve route).  The minimum-phase chain also runs at 128 and 512,
+whose transforms of 4 x 128 = 2^9 and 2^11 points have an odd log2 -- the single radix-2 stage in front of the radix-4
+passes (minphase_sub_first), which no size with an even log2 reaches -- and at 8192, eight workgroups per transform.
+
+Measured on an MI355X, minimum-phase taps against the oracle in parts of the peak tap (bound 2e-7), mid / side:
+  64: 4.6e-8 / 4.2e-8, 128: 1.3e-8 / 1.2e-8, 512: 2.0e-8 / 2.6e-8, 1024: 3.3e-8 / 3.7e-9, 2048: 1.1e-8 / 8.6e-9,
+  4096: 5.3e-9 / 2.2e-8, 8192: 4.1e-8 / 3.7e-9, 16384: 5.0e-9 / 2.6e-9.
 """
 
 import ctypes
@@ -18,7 +24,8 @@ from conftest import rms_error
 pytestmark = pytest.mark.gpu
 
 RMS_TOL = 1e-5                  # the project's bar, float32 against the float64 oracle
-SECONDS = {64: 2.0, 1024: 2.0, 2048: 2.0, 4096: 2.5, 16384: 3.0}
+SECONDS = {64: 2.0, 128: 2.0, 512: 2.0, 1024: 2.0, 2048: 2.0, 4096: 2.5, 8192: 2.5, 16384: 3.0}
+PAIR = {64: 40, 1024: 41, 2048: 42, 4096: 43, 16384: 44, 128: 45, 512: 46, 8192: 47}      # make_pair's seed of a size
 HALF = dict(amount=0.5, max_boost_db=6.0, max_cut_db=6.0)
 
 
@@ -40,7 +47,7 @@ def pairs():
 
     def get(fft):
         if fft not in cache:
-            cache[fft] = make_pair(SECONDS[fft], 44100, 40 + sorted(SECONDS).index(fft), reference_seconds=SECONDS[fft] - 0.4)
+            cache[fft] = make_pair(SECONDS[fft], 44100, PAIR[fft], reference_seconds=SECONDS[fft] - 0.4)
         return cache[fft]
 
     return get
@@ -115,7 +122,7 @@ def test_shaped_linear_taps(dev, pairs, curves, fft):
 
 
 # ---- (b) the transform chain in isolation ------------------------------------------------------------------------------
-@pytest.mark.parametrize("fft", [64, 1024, 2048, 4096, 16384])
+@pytest.mark.parametrize("fft", [64, 128, 512, 1024, 2048, 4096, 8192, 16384])
 def test_minimum_phase_chain(dev, pairs, fft):
     """The minimum-phase taps against eq_oracle's minimum phase of the SAME run's float32 linear taps: <= 2e-7 of the
     peak -- one float32 rounding, 6e-8, with margin for the float64 transforms."""

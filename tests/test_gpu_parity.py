@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import mastering_oracle as mo
+from boundary_cases import expected_previews          # (preview_creator.py + dsp.py restated in float64)
 from cases import CASES, build_inputs, oracle_params
 from conftest import rms_error
 
@@ -581,27 +582,6 @@ def test_process_files_end_to_end(tmp_path):
     assert got_pr.shape == (size, 2) and got_pt.shape == (size, 2)
     assert rms_error(got_pr, want_r) <= 3e-5 and rms_error(got_pt, want_t) <= 3e-5       # 16-bit files
     assert np.abs(got_pr - want_r).max() <= 1.5 / 32768 and np.abs(got_pt - want_t).max() <= 1.5 / 32768
-
-
-def expected_previews(target, result, size, step, fade, threshold):
-    """preview_creator.py:30-94 + dsp.py:128-152 restated on host arrays (float64)."""
-    result = np.asarray(result, dtype=np.float64)
-    n = result.shape[0]
-    if size > n:
-        starts, size = np.array([0]), n
-    else:
-        starts = np.arange((n - size) // step + 1) * step
-    rms = [np.sqrt(np.mean(result[s:s + size] ** 2)) for s in starts]
-    begin = int(starts[int(np.argmax(rms))])
-    pieces = []
-    for x in (np.clip(np.asarray(target, dtype=np.float64), -threshold, threshold), result):
-        piece = x[begin:begin + size].copy()
-        if size != n:
-            ramp = np.linspace(0, 1, fade)
-            piece[:fade] *= ramp[:, None]
-            piece[size - fade:] *= ramp[::-1, None]
-        pieces.append(piece)
-    return begin, pieces[0], pieces[1]
 
 
 def test_previews_are_cut_on_the_device(tmp_path):
