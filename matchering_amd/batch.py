@@ -13,8 +13,8 @@ axis shards without any data-path collective:
   direction at a time; the other lanes fill those holes with other pairs' work (three by default: eight
   resident 4-minute pairs take 2.6 / 2.1 / 1.85 ms with one / two / three; ``MAX_LANES`` says why not many);
 * around the GPU: reading and writing audio files is host work, so ``process_batch`` keeps ``io_threads``
-  loaders ahead of the lanes and writes results behind them.  Integer PCM goes to the GPU as the file
-  holds it and comes back quantised (``stages.main``), which leaves the host little more than file I/O.
+  loaders ahead of the lanes (``intake``'s host step there, its device step on the lane) and writes results
+  behind them (``delivery.write_results``).
 
 ``master_many`` works on arrays in memory, ``process_batch`` on files with the reference's
 ``Result`` objects.  Command line (one rank)::
@@ -426,137 +426,47 @@ def _job_profile(job):
     return given if isinstance(given, ReferenceProfile) else ReferenceProfile.load(given)
 
 
-class _Later:
-    """What ``_load_job`` left to the lane that masters the job, per track the file's rate when the track is still
-    as its file holds it (None: it is the final track already)."""
-
-    def __init__(self, target_rate=None, reference_rate=None, equality=False):
-        self.target_rate, self.reference_rate, self.equality = target_rate, reference_rate, equality
-
-
-def _on_the_lane(target, reference, later, device_index, lane, config, master):
-    """The part of checker.check that ``_load_job`` left out: upload the tracks it kept as their files hold them on
-    the lane's device, convert them there when they are mono or off-rate (``Device.track_frames``, queued on the
-    lane's handle), take the target's count_max_peaks there (mgx_peak_count) and warn as the reference would; the
-    resident frames go on to stages.main.  With a stand-in for the GPU the statistics are taken on the host."""
-    from .audio_io import unpack24
-    from .checker import check_equality, count_max_peaks, peak_warnings
-
-    if master is not None:
-        peak_warnings(count_max_peaks(unpack24(target) if target.dtype == np.uint8 else target), config)
-        return target, reference
-    dev = lane_device(device_index, lane)
-    internal = config.internal_sample_rate
-    on_device = [None, None]
-    try:
-        with dev.lock:
-            for slot, (audio, rate) in enumerate(((target, later.target_rate), (reference, later.reference_rate))):
-                if rate is not None:                   # (never a profile's: _load_job leaves its rate None)
-                    on_device[slot] = dev.track_frames(audio, rate, internal)
-            if on_device[0] is not None:
-                peaks = dev.peak_count(on_device[0], 2 * on_device[0].frames)
-        if later.equality:
-            check_equality(target, reference, [frames if frames is not None and _changes(audio, rate, internal) else None
-                                               for frames, audio, rate in ((on_device[0], target, later.target_rate),
-                                                                           (on_device[1], reference, later.reference_rate))])
-        if on_device[0] is not None:
-            peak_warnings(peaks, config)
-    except Exception:
-        for frames in on_device:
-            if frames is not None:
-                frames.release()
-        raise
-    return (on_device[0] if on_device[0] is not None else target,
-            on_device[1] if on_device[1] is not None else reference)
-
-
-def _changes(audio, rate, internal):
-    """Whether the device changes the track's rate or channels (its host array is then not the final track)."""
-    from .audio_io import pcm_channels
-
-    return rate != internal or pcm_channels(audio) != 2
-
-
-def _wanted_encodings(results):
-    from .core import _wanted_encodings as of_results
-
-    return of_results(results)
-
-
-def _needs_of(results):
-    return (any(r.use_limiter for r in results),
-            any(not r.use_limiter and not r.normalize for r in results),
-            any(not r.use_limiter and r.normalize for r in results))
-
-
 def _load_job(job, config, gpu=False, shared=False):
-    """Load + check both files of a job (core.py:52-74), on a host thread.  Returns (target, reference,
-    later): with ``later`` (a ``_Later``) a track is still as its file holds it and goes to the GPU that way.  A job
-    with a "reference_profile" or "references", or whose reference file is ``shared`` with other jobs
-    (``process_batch``'s ``share_references``), loads its target only: ``reference`` is then the ``ReferenceProfile`` / a
-    ``_ReferenceSet`` / a ``_SharedReference``, and the equality check of checker.py:140-142, which needs the reference's audio, is not made.  The
-    target's peak statistics (checker.py:118-130) are then left to the lane that masters it (``mgx_peak_count``),
-    and with ``gpu`` so is the conversion of a mono or off-rate track (``device.takes_resident``, the rule
-    ``core.process`` uses): a loader thread never spends seconds in the host resampler while its lane idles."""
-    from .audio_io import load, pcm_channels
-    from .checker import LATER, check, check_equality
+    """``intake``'s host step for both files of a job, on a loader thread.  Returns (target, reference, guard): the
+    ``intake.Track``s, and whether the equality guard is left to the lane because it needs the frames the device converts
+    (one that does not has run here, and fails the job before it takes a lane).  A job with a "reference_profile" or
+    "references", or whose reference file is ``shared`` with other jobs (``process_batch``'s ``share_references``), loads
+    its target only: ``reference`` is then the ``ReferenceProfile`` / a ``_ReferenceSet`` / a ``_SharedReference``."""
+    from . import intake
     from .utils import get_temp_folder
 
-    internal = config.internal_sample_rate
     temp_folder = config.temp_folder if config.temp_folder else get_temp_folder(job["results"])
-
-    def on_the_lane(audio, rate):
-        """(the track stays as its file holds it, its final frame count)"""
-        if gpu:
-            from .device import final_frames, takes_resident
-
-            if takes_resident(audio, rate, internal):
-                return True, final_frames(audio, rate, internal)
-            return False, None
-        return ((audio.dtype.kind in "iu" or audio.dtype == np.float32) and pcm_channels(audio) == 2
-                and rate == internal), audio.shape[0]
-
-    # (pcm=True: 16/24/32-bit WAVE samples stay integers up to the GPU, as in core.process)
-    target, rate_t = load(job["target"], "target", temp_folder, pcm=True)
-    file_rate_t = rate_t
-    deferred, frames_t = on_the_lane(target, rate_t)
-    convert_t = deferred and _changes(target, rate_t, internal)
-    target, rate_t = check(target, rate_t, config, "target", peaks=LATER if deferred else None, on_device=convert_t)
+    target = intake.read(job["target"], "target", config, temp_folder, gpu, host_peaks=True)
     profile = _job_profile(job)
     several = _ReferenceSet(job["references"]) if job.get("references") is not None else None
     if profile is not None or several is not None or shared:
         if profile is not None:
             profile.matches(config)
-        frames_t = frames_t if convert_t else target.shape[0]
-        if rate_t != internal or not (convert_t or pcm_channels(target) == 2) or not frames_t > config.fft_size:
-            raise ModuleError(Code.ERROR_VALIDATION)
-        if not config.allow_equality:
-            from .core import NO_EQUALITY_CHECK
-
-            debug(NO_EQUALITY_CHECK)
+        intake.validate(config, target)
+        intake.no_equality_check(config)
         stand_in = profile if profile is not None else (several if several is not None else _SharedReference(job["reference"]))
-        return target, stand_in, (_Later(file_rate_t, None, False) if deferred else None)
-    reference, rate_r = load(job["reference"], "reference", temp_folder, pcm=True)
-    file_rate_r = rate_r
-    convert_r, frames_r = on_the_lane(reference, rate_r)
-    convert_r = convert_r and _changes(reference, rate_r, internal)      # (a reference that is final goes up in stages.main)
-    reference, rate_r = check(reference, rate_r, config, "reference", on_device=convert_r)
-    frames_t = frames_t if convert_t else target.shape[0]
-    frames_r = frames_r if convert_r else reference.shape[0]
-    equality = False
-    if not config.allow_equality:
-        if convert_t or convert_r:
-            equality = frames_t == frames_r        # (tracks of unequal length are not equal; else the lane compares them)
-        else:
-            check_equality(target, reference)
-    if (not (rate_t == rate_r == internal)
-            or not ((convert_t or pcm_channels(target) == 2) and (convert_r or pcm_channels(reference) == 2))
-            or not (frames_t > config.fft_size and frames_r > config.fft_size)):
-        raise ModuleError(Code.ERROR_VALIDATION)
-    later = None
-    if deferred or convert_r:
-        later = _Later(file_rate_t if deferred else None, file_rate_r if convert_r else None, equality)
-    return target, reference, later
+        return target, stand_in, False
+    reference = intake.read(job["reference"], "reference", config, temp_folder, gpu)
+    guard = intake.guard_needs_frames(target, reference, config)
+    if not guard:
+        intake.equality_guard(target, reference, config)
+    intake.validate(config, target, reference)
+    return target, reference, guard
+
+
+def _finish_tracks(target, reference, guard, dev, config):
+    """``intake``'s device step for a job's tracks on the lane's device (``dev``: None with a stand-in for the GPU), then
+    the equality guard ``_load_job`` left: what ``stages.main`` receives."""
+    from . import intake
+
+    with intake.released_on_error(target, reference):
+        target.to_device(dev, config)
+        if isinstance(reference, intake.Track):
+            reference.to_device(dev, config)
+            if guard:
+                intake.equality_guard(target, reference, config)
+            reference = reference.for_main
+    return target.for_main, reference
 
 
 class _WithDeliveries(tuple):
@@ -566,18 +476,6 @@ class _WithDeliveries(tuple):
         self = super().__new__(cls, triple)
         self.deliveries = deliveries
         return self
-
-
-def _save_job(job, triple, config, deliveries=None):
-    from .audio_io import save
-    from .delivery import plain_results, write_deliveries
-
-    result, plain, normalized = triple
-    for wanted in plain_results(job["results"]):
-        chosen = result if wanted.use_limiter else (normalized if wanted.normalize else plain)
-        save(wanted.file, chosen, config.internal_sample_rate, wanted.subtype)
-    if deliveries:                                 # (each at its delivery's own rate)
-        write_deliveries(job["results"], deliveries, config.internal_sample_rate)
 
 
 def process_batch(jobs, config=None, rank=None, world_size=None, device_index=None, lanes=None, io_threads=4,
@@ -595,6 +493,7 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     its exception is re-raised (after the jobs already in flight have finished).  ``eq``: the ``eq.MatchingEq`` of every
     job that has no "eq" of its own (an ``eq.MatchingEq`` or the JSON object of one); what the library refuses is a
     ValueError before a file is read."""
+    from .delivery import DeliveryRequest, renderings_wanted, write_results
     from .eq import as_eq
 
     config = config if config is not None else Config()
@@ -609,8 +508,6 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
         if eqs[i] is not None:
             eqs[i].check(config)
         # (a delivery rate the device converter refuses is a ValueError here, before a file is read)
-        from .delivery import DeliveryRequest
-
         DeliveryRequest.for_results(jobs[i]["results"]).check_rates(config.internal_sample_rate)
     device_index = local if device_index is None else device_index
     savers = []
@@ -656,7 +553,7 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                 return ReferenceProfile.merge(sources, device=None if master is not None else lane_device(device_index, lane))
 
             def run(item):
-                index, (target, reference, later) = item
+                index, (target, reference, guard) = item
                 if isinstance(reference, _SharedReference):
                     reference = analysed(reference.path, profiles)
                 elif isinstance(reference, _ReferenceSet):
@@ -666,18 +563,12 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                         if reference.key not in merged:
                             merged[reference.key] = merged_set(reference)
                         reference = merged[reference.key]
-                from .delivery import DeliveryRequest, plain_results
-
-                # (results with a delivery come back in the job's DeliveryRequest: they decide neither which renderings
-                # are returned nor their encodings)
-                ordinary = plain_results(jobs[index]["results"])
                 deliveries = DeliveryRequest.for_results(jobs[index]["results"])
-                needs = _needs_of(ordinary)
-                key = (needs, _wanted_encodings(ordinary))
+                key = renderings_wanted(jobs[index]["results"])
                 if key not in workers:
-                    workers[key] = _device_worker(device_index, lane, config, needs, master, key[1])
-                if later is not None:
-                    target, reference = _on_the_lane(target, reference, later, device_index, lane, config, master)
+                    workers[key] = _device_worker(device_index, lane, config, key[0], master, key[1])
+                target, reference = _finish_tracks(target, reference, guard,
+                                                 None if master is not None else lane_device(device_index, lane), config)
                 shaped = {} if eqs[index] is None else {"eq": eqs[index]}
                 if not deliveries:
                     return workers[key]((target, reference), **shaped)
@@ -696,7 +587,8 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
         def done(index, triple, exc):
             if exc is None:
                 unsaved.acquire()
-                future = io.submit(_save_job, jobs[index], tuple(triple), config, getattr(triple, "deliveries", None))
+                future = io.submit(write_results, jobs[index]["results"], tuple(triple), config.internal_sample_rate,
+                                   getattr(triple, "deliveries", None))
                 future.add_done_callback(lambda _f: unsaved.release())
                 savers.append(future)
 

@@ -58,6 +58,20 @@ def _resample(array, sample_rate, required):
         return resample(array, sample_rate, required)
 
 
+def on_host(array, sample_rate, internal_sample_rate):
+    """A track of one or two channels as its file holds it -> two channels at the internal rate, on the host: packed
+    24-bit samples unpacked, a mono track repeated (dsp.py:45-46), an off-rate one resampled in float64 like the arrays
+    soundfile hands the reference's resampler (checker.py:42), also when the file arrives as float32 (FLOAT WAVE, 8-bit
+    PCM)."""
+    if array.dtype == np.uint8:
+        array = unpack24(array)
+    if pcm_channels(array) == 1:
+        array = np.repeat(array, repeats=2, axis=1)
+    if sample_rate != internal_sample_rate:
+        array = _resample(np.asarray(pcm_to_float(array, np.float64), dtype=np.float64), sample_rate, internal_sample_rate)
+    return array
+
+
 LATER = object()      # check(..., peaks=LATER): the caller will hand the peak statistics to peak_warnings itself
 
 
@@ -98,23 +112,20 @@ def check(array: np.ndarray, sample_rate: int, config: Config, name: str, peaks=
     converting = channels != 2 or sample_rate != config.internal_sample_rate
     if converting and peaks is LATER and not on_device:
         peaks = None                                                    # (taken below, on the converted track)
-    if not on_device and array.dtype == np.uint8 and (converting or (target and peaks is None)):
-        array = unpack24(array)                                         # packed samples: only as they are, or not
     if channels == 1:
         info(Code.INFO_TARGET_IS_MONO if target else Code.INFO_REFERENCE_IS_MONO)
-        if not on_device:
-            array = np.repeat(array, repeats=2, axis=1)                 # dsp.py:45-46
     elif channels != 2:
         raise ModuleError(Code.ERROR_TARGET_NUM_OF_CHANNELS_IS_EXCEEDED if target
                           else Code.ERROR_REFERENCE_NUM_OF_CHANNELS_IS_EXCEEDED)
-
-    if sample_rate != config.internal_sample_rate:
+    off_rate = sample_rate != config.internal_sample_rate
+    if off_rate:                      # (said in front of the conversion, which may take seconds on the host)
         debug(f"{name}: converting {sample_rate} Hz -> {config.internal_sample_rate} Hz")
-        # float64 like the arrays soundfile hands the reference's resampler (checker.py:42), also for files
-        # that arrive as float32 (FLOAT WAVE, 8-bit PCM)
-        if not on_device:
-            array = _resample(np.asarray(pcm_to_float(array, np.float64), dtype=np.float64), sample_rate,
-                              config.internal_sample_rate)
+    if not on_device:
+        if converting:
+            array = on_host(array, sample_rate, config.internal_sample_rate)
+        elif array.dtype == np.uint8 and target and peaks is None:
+            array = unpack24(array)                                     # packed samples: only as they are, or not
+    if off_rate:
         if target:
             warning(Code.WARNING_TARGET_IS_RESAMPLED)
         else:

@@ -39,9 +39,11 @@ quantiser needs (``mgx_delivery_gain_shaped``), so the c
 
 import ctypes
 import math
+import os
 from dataclasses import dataclass, field, fields
 from functools import lru_cache
 
+from .audio_io import save
 from .loudness import Loudness, _db
 
 DITHERS = {None: 0, "tpdf": 1, "tpdf_hp": 2}
@@ -443,11 +445,38 @@ def plain_results(results):
     return [item for item in results if getattr(item, "delivery", None) is None]
 
 
+def file_encoding(item):
+    """The integer subtype of one WAVE file (quantised on the GPU, ``mgx_pcm_encode``), or None (float frames, host
+    codec: saver.py:27-33)."""
+    if item is None or os.path.splitext(item.file)[1][1:].upper() not in ("WAV", "WAVE"):
+        return None
+    return item.subtype if item.subtype in SUBTYPE_BITS else None
+
+
+def renderings_wanted(results):
+    """(needs, encodings) of ``stages.main`` for a list of results.  ``needs``: which of its three outputs the files need
+    (core.py:77-86); ``encodings``: per output the PCM subtype the GPU can quantise to directly -- every file made from
+    that rendering is a WAVE file of one and the same integer subtype -- else None.  Results with a delivery are cut
+    from the renderings in HBM and come back in the ``DeliveryRequest``: they take no part in either."""
+    wanted = [set(), set(), set()]
+    for item in plain_results(results):
+        wanted[rendering_of(item)].add(file_encoding(item))
+    return tuple(bool(w) for w in wanted), tuple(next(iter(w)) if len(w) == 1 else None for w in wanted)
+
+
+def write_results(results, renderings, sample_rate, deliveries=None):
+    """One file per Result, each from the rendering it asked for (core.py:95-108); a Result with a delivery from the
+    array ``stages.main`` left in the ``DeliveryRequest``, at its delivery's own rate."""
+    for item in plain_results(results):
+        save(item.file, renderings[rendering_of(item)], sample_rate, item.subtype)
+    if deliveries:
+        write_deliveries(results, deliveries, sample_rate)
+
+
 def write_deliveries(results, request, sample_rate):
     """One file per Result that carries a delivery, from the arrays ``stages.main`` left in ``request``, each at its own
     rate (``sample_rate``: the internal one, for the deliveries that name none); one log line each: gain, achieved LUFS
     and dBTP, and the shortfall where the ceiling bound the loudness."""
-    from .audio_io import save
     from .log import debug
 
     for item in results:

@@ -59,25 +59,10 @@ def from_report(report, sample_rate, frames):
 
 
 def _path_frames(path, config, dev):
-    """A file -> ``DeviceFrames`` at the internal rate by ``process``'s own route for a track: loaded, taken resident
-    and decoded on the device where ``device.takes_resident`` says so, converted there when off-rate or mono; the host
-    converts the rest, as ``checker.check`` does."""
-    from .audio_io import load, pcm_channels, pcm_to_float, unpack24
-    from .checker import _resample
-    from .device import DeviceFrames, takes_resident
+    """A file -> ``DeviceFrames`` at the internal rate by ``process``'s own route for a track (``intake.file_frames``)."""
+    from . import intake
 
-    internal = config.internal_sample_rate
-    temp_folder = config.temp_folder or os.path.dirname(os.path.abspath(path))
-    audio, rate = load(path, "target", temp_folder, pcm=True)
-    if takes_resident(audio, rate, internal):
-        return dev.track_frames(audio, rate, internal)
-    if audio.dtype == np.uint8:
-        audio = unpack24(audio)
-    if pcm_channels(audio) == 1:
-        audio = np.repeat(audio, repeats=2, axis=1)
-    if rate != internal:
-        audio = _resample(np.asarray(pcm_to_float(audio, np.float64), dtype=np.float64), rate, internal)
-    return DeviceFrames(dev.upload_frames(audio), audio.shape[0])
+    return intake.file_frames(path, config, config.temp_folder or os.path.dirname(os.path.abspath(path)), dev)
 
 
 def measure(source, sample_rate=None, config: Config = None, device=None):

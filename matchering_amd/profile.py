@@ -257,9 +257,8 @@ class ReferenceProfile:
 
 
 def _load_reference(path, config, dev):
-    """``process``'s route for a reference file (core.read_track): ``DeviceFrames`` or a checked host array."""
-    from .core import read_track
+    """``process``'s route for a reference file (``intake``): ``DeviceFrames`` or a checked host array."""
+    from . import intake
 
     temp_folder = config.temp_folder or os.path.dirname(os.path.abspath(os.fspath(path)))
-    array, frames = read_track(path, "reference", config, temp_folder, dev)
-    return frames if frames is not None else array
+    return intake.read_single(path, "reference", config, temp_folder, dev).for_main

@@ -258,3 +258,79 @@ def test_a_file_as_its_own_reference_at_an_off_rate(tmp_path):
                             mg.Config(), lanes=1, io_threads=1)
     assert same.value.code == Code.ERROR_TARGET_EQUALS_REFERENCE
     assert not os.path.exists(str(tmp_path / "never.wav"))
+
+
+# ---- process and process_batch on one intake: the same files from every kind of file -----------------------------------
+# (byte identity and equal codes held for every case at the commit before intake.py, where the two had loaders of their own)
+KINDS = {   # case -> (target, reference), each (subtype, rate, channels, clipped)
+    "A": (("PCM_24", 44100, 1, True), ("FLOAT", 44100, 2, False)),     # on-rate mono column fill; float32 as it is
+    "B": (("PCM_32", 48000, 2, False), ("PCM_16", 22050, 1, False)),   # the host's float64 resampler beside the device's
+    "C": (("FLOAT", 48000, 2, False), ("PCM_24", 44100, 2, False)),    # a converted target, a resident unchanged reference
+}
+
+
+def _kind_file(tmp_path, name, kind, seed):
+    subtype, rate, channels, clipped = kind
+    audio = synth(0.5, rate, seed)
+    audio = np.clip(8.0 * audio, -1.0, 1.0) if clipped else 0.5 * audio
+    path = str(tmp_path / f"{name}.wav")
+    audio_io.write_wav(path, audio[:, :channels], rate, subtype)
+    return path
+
+
+def _codes_of(call):
+    seen = []
+    mg.log(warning_handler=seen.append, info_handler=seen.append, show_codes=True)
+    try:
+        call()
+    finally:
+        mg.log()
+    # (loading, exporting and completed are lines of ``process`` alone)
+    return sorted(code for code in (str(line).split(":")[0] for line in seen) if code not in ("2003", "2008", "2010"))
+
+
+def _same_files_and_codes(tmp_path, config, target, reference, job_reference):
+    single, many = str(tmp_path / "single.wav"), str(tmp_path / "batch.wav")
+    codes = _codes_of(lambda: mg.process(target, reference, [mg.pcm24(single)], config))
+    job = {"target": target, "results": [mg.pcm24(many)], **job_reference}
+    batch_codes = _codes_of(lambda: batch.process_batch([job], config, lanes=1, io_threads=1))
+    print(f"process: {codes}\nprocess_batch: {batch_codes}")
+    with open(single, "rb") as a, open(many, "rb") as b:
+        assert a.read() == b.read()
+    assert codes == batch_codes and codes
+
+
+@pytest.mark.parametrize("case", sorted(KINDS))
+def test_batch_writes_the_files_process_writes_from_every_kind(tmp_path, case):
+    target = _kind_file(tmp_path, "target", KINDS[case][0], 41)
+    reference = _kind_file(tmp_path, "reference", KINDS[case][1], 42)
+    _same_files_and_codes(tmp_path, mg.Config(), target, reference, {"reference": reference})
+
+
+def test_batch_writes_the_files_process_writes_against_a_profile(tmp_path):
+    from matchering_amd.profile import ReferenceProfile
+
+    config = mg.Config()
+    target = _kind_file(tmp_path, "target", KINDS["B"][0], 41)
+    reference = _kind_file(tmp_path, "reference", KINDS["B"][1], 42)
+    saved = str(tmp_path / "reference.profile")
+    ReferenceProfile.analyze(reference, config).save(saved)
+    _same_files_and_codes(tmp_path, config, target, saved, {"reference_profile": saved})
+
+
+def test_measure_hears_a_file_as_process_does(tmp_path, dev):
+    """``loudness.measure(path)``: a file the device takes goes through ``Device.track_frames``, any other through the
+    host conversion ``checker.check`` makes."""
+    config = mg.Config()
+    internal = config.internal_sample_rate
+    target = _kind_file(tmp_path, "target", KINDS["B"][0], 41)
+    reference = _kind_file(tmp_path, "reference", KINDS["B"][1], 42)
+    audio, rate = audio_io.load(reference, "reference", str(tmp_path), pcm=True)
+    with dev.lock:
+        frames = dev.track_frames(audio, rate, internal)
+    try:
+        assert mg.measure(reference, config=config) == mg.measure(frames, internal, config)
+    finally:
+        frames.release()
+    audio, rate = audio_io.load(target, "target", str(tmp_path), pcm=True)
+    assert mg.measure(target, config=config) == mg.measure(checker.check(audio, rate, config, "target")[0], internal, config)

@@ -123,7 +123,7 @@ def test_stages_main_refuses_a_foreign_profile_before_any_launch(monkeypatch):
 def test_process_passes_a_profile_through(tmp_path, monkeypatch, how):
     """core.process with a profile in the reference's place: only the target is loaded and checked, check_equality is
     not called (and a debug line says so), the profile reaches ``main`` as it is, the log codes keep their order."""
-    from matchering_amd import checker, core
+    from matchering_amd import checker, core, intake
     from matchering_amd.profile import ReferenceProfile
     from matchering_amd.synth import make_pair
 
@@ -146,7 +146,7 @@ def test_process_passes_a_profile_through(tmp_path, monkeypatch, how):
         return np.zeros((target.shape[0], 2), np.float32), None, None
 
     loaded = []
-    real_load = core.load
+    real_load = intake.load
 
     def spy_load(path, role, *args, **kwargs):
         loaded.append(role)
@@ -157,8 +157,8 @@ def test_process_passes_a_profile_through(tmp_path, monkeypatch, how):
 
     monkeypatch.setattr(core, "main", fake_main)
     monkeypatch.setattr(core, "_gpu", lambda: None)
-    monkeypatch.setattr(core, "load", spy_load)
-    monkeypatch.setattr(core, "check_equality", no_equality)
+    monkeypatch.setattr(intake, "load", spy_load)
+    monkeypatch.setattr(intake, "check_equality", no_equality)
     monkeypatch.setattr(checker, "check_equality", no_equality)
     codes, lines = [], []
     mg.log(info_handler=lambda text: codes.append(int(str(text).split(":")[0])), debug_handler=lines.append,

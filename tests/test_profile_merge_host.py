@@ -106,7 +106,7 @@ def test_analyze_makes_a_profile_of_every_element_and_merges(tmp_path, monkeypat
 def test_process_takes_a_set_in_the_references_place(tmp_path, monkeypatch):
     """Only the target is loaded by ``process`` itself; the set's own files go through ``ReferenceProfile.analyze``
     (per element) and ``merge``; ``main`` receives the merged profile; check_equality cannot run and a debug line says so."""
-    from matchering_amd import checker, core
+    from matchering_amd import checker, core, intake
     from matchering_amd.profile import ReferenceProfile
     from matchering_amd.synth import make_pair
 
@@ -126,7 +126,7 @@ def test_process_takes_a_set_in_the_references_place(tmp_path, monkeypatch):
         seen["reference"] = reference
         return np.zeros((target.shape[0], 2), np.float32), None, None
 
-    real_load = core.load
+    real_load = intake.load
 
     def spy_load(path, role, *args, **kwargs):
         loaded.append(role)
@@ -138,8 +138,8 @@ def test_process_takes_a_set_in_the_references_place(tmp_path, monkeypatch):
     monkeypatch.setattr(ReferenceProfile, "merge", staticmethod(fake))
     monkeypatch.setattr(core, "main", fake_main)
     monkeypatch.setattr(core, "_gpu", lambda: None)
-    monkeypatch.setattr(core, "load", spy_load)
-    monkeypatch.setattr(core, "check_equality", no_equality)
+    monkeypatch.setattr(intake, "load", spy_load)
+    monkeypatch.setattr(intake, "check_equality", no_equality)
     monkeypatch.setattr(checker, "check_equality", no_equality)
     codes, lines = [], []
     mg.log(info_handler=lambda text: codes.append(int(str(text).split(":")[0])), debug_handler=lines.append, show_codes=True)

@@ -29,7 +29,7 @@ def main():
         return batch_wall(args)
 
     import matchering_amd as mg
-    from matchering_amd import audio_io, core
+    from matchering_amd import audio_io, core, delivery, intake
     from matchering_amd.synth import make_pair
 
     target, reference = make_pair(args.seconds, 44100, pair=0)
@@ -54,9 +54,10 @@ def main():
 
         setattr(module, name, wrapper)
 
-    for name, label in (("load", "load"), ("check", "check"), ("check_equality", "check_equality"), ("main", "stages.main"),
-                        ("save", "save")):
-        timed(core, name, label)
+    # (the names the intake, ``process`` and the writer call them by)
+    for module, name, label in ((intake, "load", "load"), (intake, "check", "check"), (intake, "check_equality", "check_equality"),
+                                (core, "main", "stages.main"), (delivery, "save", "save")):
+        timed(module, name, label)
 
     print(f"{frames} frames per track ({args.seconds:.0f} s at 44.1 kHz), {args.subtype} in, {args.subtype} out")
     for run in range(args.runs):
