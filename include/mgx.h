@@ -543,6 +543,78 @@ int mgx_delivery_limit_step_shaped(const mgx_delivery* delivery, const mgx_noise
 int mgx_deliver_shaped(mgx_handle* h, const float* x_dev, int64_t n_frames, double gain, int32_t bits,
                        const mgx_noise_shaper* shaper, uint64_t seed, void* out_dev);
 
+/* Audit: the quality-control pass a distributor's intake check makes, over frames or file PCM that are still in HBM -- DC
+ * offset, runs of samples at the rail, a stereo image that cancels in mono, dropouts, head and tail silence, samples that
+ * are not finite numbers (the reference's checker counts the samples on the peak and nothing else; mgx_loudness gives
+ * loudness and peaks).  Part of the new surface, like the meter.  DESIGN.md section 3.17.
+ *   input: n stereo frames, interleaved.  bits 0: float32; bits 16, 24, 32: file PCM as mgx_pcm_decode reads it
+ *     (little-endian, 24-bit packed in three bytes).  An integer sample v has the value v / 2^(bits-1) as a double, so
+ *     32-bit samples are exact; all arithmetic on values is float64, every product rounded once and every sum on its own
+ *     (no fused multiply-add).
+ *   limits: clip_level (linear, > 0), clip_run (>= 1), silence_level (linear, >= 0; 0: exact zeros only).
+ *   per sample: non-finite = NaN or +-Inf (bits 0 only); at the rail = finite and |x| >= clip_level; a frame is silent
+ *     when both samples are finite and |x| <= silence_level.  A non-finite sample is counted in nonfinite[c], left out of
+ *     every sum and of peak, is not at the rail and makes its frame not silent.
+ *   per channel c: sum[c], sumsq[c]; peak[c] = max |x| over the finite samples; nonfinite[c].  A run is a maximal
+ *     sequence of consecutive at-rail samples of one channel, of either sign; an event is a run of length >= clip_run.
+ *     clip_events[c] = events, clip_samples[c] = samples inside events, clip_longest[c] = the longest run of any length
+ *     (0: none), clip_first[c] = the frame of the first event's first sample (-1: none).
+ *   stereo: sum_lr = sum of L R over the frames whose samples are both finite.
+ *   silence: head_silence = silent frames before the first frame that is not (n when every frame is silent),
+ *     tail_silence the same from the end; gap_longest / gap_at = the longest run of silent frames strictly between the
+ *     first and the last non-silent frame and where it starts (0 and -1: none; of equal runs the earliest).
+ *   sub-blocks: B = (sample_rate + 5) / 10 frames -- the meter's grid, rounded as mgx_loudness rounds it (sample_rate / 10
+ *     wherever the rate is a multiple of 10).  sub_sums[k] = {sum L^2, sum R^2, sum L R} over sub-block k,
+ *     k < (n + B - 1) / B: unlike the meter's, the last, partial sub-block is included; n implies its length.
+ *   mgx_audit_gate, the device-free rule, from the report's sums and the sub-block sums:
+ *     dc[c] = sum[c] / n;  rms[c] = sqrt(sumsq[c] / n);  balance_db = 10 log10(sumsq[0] / sumsq[1]);
+ *     correlation = sum_lr / sqrt(sumsq[0] sumsq[1]);
+ *     mono_loss_db = 10 log10((sumsq[0] + sumsq[1] + 2 sum_lr) / (2 (sumsq[0] + sumsq[1]))): (L + R) / 2 against the mean
+ *       channel power (a numerator that rounds below 0 counts as 0: -infinity);
+ *     correlation_min / correlation_min_at = the minimum, and the index of its first sub-block, of the correlation over
+ *       windows of 30 consecutive sub-blocks stepping one (each window's three sums added in sub-block order); a window
+ *       whose mean power (sum L^2 + sum R^2) / (2 frames) is below 10^-7 (-70 dB) or one of whose channel sums is 0 is
+ *       skipped; a track of fewer than 30 sub-blocks has the one window of all of them; of equal minima the earliest.
+ *       Where nothing qualifies: NaN and -1.  Every ratio above is NaN where its denominator is 0 (n == 0 included).
+ * mgx_audit: two launches on the handle's stream (csrc/audit_kernel.h), none of whose workgroups waits for another; it
+ * waits for the result, fills the measured fields and applies mgx_audit_gate, so the report is complete.  Two calls on
+ * the same input give the same bits.  sub_sums (host, [capacity][3], may be NULL) receives the sub-block sums and
+ * *count (may be NULL) their number.  n_frames == 0 succeeds, launches nothing and gives zero counts and sums, positions
+ * -1 and NaN ratios.  MGX_ERR_ARGUMENT, the message naming the field: a null h, limits, report or (n_frames > 0) x_dev;
+ * x_dev not 16-byte aligned (what mgx_malloc returns is); n_frames negative; bits outside {0, 16, 24, 32}; sample_rate
+ * below 8000; clip_level not finite or <= 0; clip_run < 1; silence_level negative or not finite; capacity below the
+ * number of sub-blocks where sub_sums is given.  MGX_ERR_UNSUPPORTED: more than 500 million frames.  The handle is good
+ * for the next call.
+ * mgx_audit_gate needs no GPU: it reads report->sum, sumsq and sum_lr and writes frames, sub_blocks, sub_block_frames
+ * and the derived figures; MGX_ERR_ARGUMENT for a null report, a negative count or n_frames, a null sub_sums with
+ * count > 0, a sample_rate below 8000, and a count that is not (n_frames + B - 1) / B. */
+typedef struct mgx_audit_limits {
+    double clip_level;                   /* linear */
+    double silence_level;                /* linear */
+    int32_t clip_run;                    /* samples */
+    int32_t reserved;
+} mgx_audit_limits;
+typedef struct mgx_audit_report {
+    int64_t frames;
+    int64_t nonfinite[2];
+    int64_t clip_events[2], clip_samples[2], clip_longest[2], clip_first[2];
+    int64_t head_silence, tail_silence, gap_longest, gap_at;
+    int64_t sub_blocks;
+    int32_t sub_block_frames;
+    int32_t bits;
+    double sum[2], sumsq[2], peak[2];
+    double sum_lr;
+    /* mgx_audit_gate's */
+    double dc[2], rms[2];
+    double balance_db, correlation, mono_loss_db;
+    double correlation_min;
+    int64_t correlation_min_at;
+} mgx_audit_report;
+int mgx_audit(mgx_handle* h, const void* x_dev, int64_t n_frames, int32_t bits, int32_t sample_rate,
+              const mgx_audit_limits* limits, mgx_audit_report* report, double* sub_sums, int64_t capacity,
+              int64_t* count);
+int mgx_audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int32_t sample_rate, mgx_audit_report* report);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

@@ -103,6 +103,48 @@ class MgxLoudnessReport(ctypes.Structure):
     ]
 
 
+class MgxAuditLimits(ctypes.Structure):
+    """mgx_audit_limits (include/mgx.h)."""
+
+    _fields_ = [
+        ("clip_level", ctypes.c_double),
+        ("silence_level", ctypes.c_double),
+        ("clip_run", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class MgxAuditReport(ctypes.Structure):
+    """mgx_audit_report (include/mgx.h)."""
+
+    _fields_ = [
+        ("frames", ctypes.c_int64),
+        ("nonfinite", ctypes.c_int64 * 2),
+        ("clip_events", ctypes.c_int64 * 2),
+        ("clip_samples", ctypes.c_int64 * 2),
+        ("clip_longest", ctypes.c_int64 * 2),
+        ("clip_first", ctypes.c_int64 * 2),
+        ("head_silence", ctypes.c_int64),
+        ("tail_silence", ctypes.c_int64),
+        ("gap_longest", ctypes.c_int64),
+        ("gap_at", ctypes.c_int64),
+        ("sub_blocks", ctypes.c_int64),
+        ("sub_block_frames", ctypes.c_int32),
+        ("bits", ctypes.c_int32),
+        ("sum", ctypes.c_double * 2),
+        ("sumsq", ctypes.c_double * 2),
+        ("peak", ctypes.c_double * 2),
+        ("sum_lr", ctypes.c_double),
+        ("dc", ctypes.c_double * 2),
+        ("rms", ctypes.c_double * 2),
+        ("balance_db", ctypes.c_double),
+        ("correlation", ctypes.c_double),
+        ("mono_loss_db", ctypes.c_double),
+        ("correlation_min", ctypes.c_double),
+        ("correlation_min_at", ctypes.c_int64),
+    ]
+
+
 class MgxDelivery(ctypes.Structure):
     """mgx_delivery (include/mgx.h)."""
 
@@ -233,6 +275,10 @@ SYMBOLS = {
     "mgx_loudness": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport), c_double_p,
                                     ctypes.c_int64, c_int64_p]),
     "mgx_loudness_gate": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(MgxLoudnessReport)]),
+    "mgx_audit": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MgxAuditLimits),
+                                 ctypes.POINTER(MgxAuditReport), c_double_p, ctypes.c_int64, c_int64_p]),
+    "mgx_audit_gate": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                      ctypes.POINTER(MgxAuditReport)]),
     "mgx_delivery_gain": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxLoudnessReport),
                                          ctypes.POINTER(MgxDeliveryResult)]),
     "mgx_deliver": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,

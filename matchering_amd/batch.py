@@ -35,7 +35,8 @@ optional: ``delivery.Delivery``; ``"dither"``: a name -- "lipshitz5" and "wannam
 ``"reference_profile"``, the path of a profile saved by ``ReferenceProfile.save`` (profile.py), or ``"references"``, a
 list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).  A job may carry
 ``"eq": {"amount": 0.5, "max_boost_db": 6, "max_cut_db": 6, "phase": "minimum"}`` (every key optional:
-``eq.MatchingEq``), the controls of its matching EQ.
+``eq.MatchingEq``), the controls of its matching EQ, and ``"audit": true``: its tracks, renderings and deliveries are
+audited (``qc.audit``) and the job carries the audits as plain dicts under ``"audit"`` afterwards.
 """
 
 import json
@@ -262,23 +263,26 @@ def _device_worker(device_index, lane, config, needs, master, encodings=None):
     """A callable mastering one (target, reference) array pair on the lane's own device handle.
     ``encodings``: stages.main's (integer PCM renderings straight from the GPU).  ``deliveries`` (per call): a job's
     ``delivery.DeliveryRequest``, handed to ``main`` where the job has one; ``eq`` (per call): the job's
-    ``eq.MatchingEq``, likewise."""
-    def extra(deliveries, eq):
+    ``eq.MatchingEq``, likewise; ``audit`` (per call): ``stages.main``'s handler, where the job asks for audits."""
+    def extra(deliveries, eq, audit):
         given = {"deliveries": deliveries} if deliveries else {}
         if eq is not None:
             given["eq"] = eq
+        if audit is not None:
+            given["audit"] = audit
         return given
 
     if master is not None:                         # tests inject a stand-in for the GPU
         if encodings is None or not any(encodings):
-            return lambda pair, deliveries=None, eq=None: master(pair[0], pair[1], config, *needs, **extra(deliveries, eq))
-        return lambda pair, deliveries=None, eq=None: master(pair[0], pair[1], config, *needs, encodings=encodings,
-                                                             **extra(deliveries, eq))
+            return lambda pair, deliveries=None, eq=None, audit=None: master(pair[0], pair[1], config, *needs,
+                                                                             **extra(deliveries, eq, audit))
+        return lambda pair, deliveries=None, eq=None, audit=None: master(pair[0], pair[1], config, *needs, encodings=encodings,
+                                                                         **extra(deliveries, eq, audit))
     from .stages import main
 
     dev = lane_device(device_index, lane)
-    return lambda pair, deliveries=None, eq=None: main(pair[0], pair[1], config, *needs, device=dev, encodings=encodings,
-                                                       **extra(deliveries, eq))
+    return lambda pair, deliveries=None, eq=None, audit=None: main(pair[0], pair[1], config, *needs, device=dev,
+                                                                   encodings=encodings, **extra(deliveries, eq, audit))
 
 
 def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
@@ -492,7 +496,9 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     the indices of the jobs this rank mastered.  The first failing job aborts the rank's batch and
     its exception is re-raised (after the jobs already in flight have finished).  ``eq``: the ``eq.MatchingEq`` of every
     job that has no "eq" of its own (an ``eq.MatchingEq`` or the JSON object of one); what the library refuses is a
-    ValueError before a file is read."""
+    ValueError before a file is read.  A job with ``"audit": True`` has every track, rendering and delivery audited
+    (``qc.audit``; the deliveries as the integer samples their files hold) and carries the audits afterwards as plain
+    dicts under ``"audit"``, keyed "target", "reference", the renderings' names and "delivered:" + file."""
     from .delivery import DeliveryRequest, renderings_wanted, write_results
     from .eq import as_eq
 
@@ -570,6 +576,10 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                 target, reference = _finish_tracks(target, reference, guard,
                                                  None if master is not None else lane_device(device_index, lane), config)
                 shaped = {} if eqs[index] is None else {"eq": eqs[index]}
+                if jobs[index].get("audit"):
+                    # "audit": true -> the job's audits as plain dicts, by the names stages.main's handler receives
+                    audits = jobs[index]["audit"] = {}
+                    shaped["audit"] = lambda name, value, kept=audits: kept.__setitem__(name, value.as_dict())
                 if not deliveries:
                     return workers[key]((target, reference), **shaped)
                 return _WithDeliveries(workers[key]((target, reference), deliveries, **shaped), deliveries)
@@ -628,6 +638,8 @@ def jobs_from_json(path):
                           delivery=None if r.get("delivery") is None else Delivery.from_json(r["delivery"]))
                    for r in item["results"]]
         job = {"target": item["target"], "results": results}
+        if item.get("audit"):
+            job["audit"] = True
         if item.get("eq") is not None:
             from .eq import MatchingEq
 

@@ -165,6 +165,7 @@ struct mgx_handle {
     std::map<int, LoudnessDev> loudness_plans;
     DevBuf loudness_out;                    // [nsub][2] sub-block energies, then [workgroups][2] peaks
     DevBuf tp_plane, tp_words;              // mgx_tp_limit: the d0 plane [tiles * T] float32; aggregates and peaks, [2][tiles] float64
+    DevBuf audit_work, audit_out;           // mgx_audit: the segments' records and sub-block shares; the totals, then [count][3] sub-block sums
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // set by a kernel whose bounded wait expired (limiter look-back, level-correction round): one word of

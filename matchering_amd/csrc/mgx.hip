@@ -30,6 +30,7 @@
 #include "deliver_kernel.h"            // (behind every other kernel: it moves none of them in the code object)
 #include "tp_limit_kernel.h"
 #include "deliver_shaped_kernel.h"
+#include "audit_kernel.h"
 
 #include "mgx_policy.h"
 #include "handle.h"
@@ -442,6 +443,56 @@ int mgx_loudness(mgx_handle* h, const float* x_dev, int64_t n, int32_t sample_ra
     loudness_fill(loudness_gate(e, g.nsub, g.S), g.nsub, g.S, report);
     if (sub_energy) std::memcpy(sub_energy, e, (size_t)g.nsub * 2 * sizeof(double));
     return 0;
+}
+
+int mgx_audit(mgx_handle* h, const void* x_dev, int64_t n_frames, int32_t bits, int32_t sample_rate,
+              const mgx_audit_limits* limits, mgx_audit_report* report, double* sub_sums, int64_t capacity,
+              int64_t* count) {
+    // everything that depends on the numbers alone is settled before the handle is touched
+    static_assert(AUDIT_SUB_MIN == (LOUD_MIN_RATE + 5) / 10, "a segment meets at most AUDIT_SUBS_MAX sub-blocks at every rate audit_request accepts");
+    int B = 0;
+    MGX_TRY(audit_request(limits, report, n_frames, bits, sample_rate, sub_sums, capacity, count, &B));
+    if (!h) return fail(MGX_ERR_ARGUMENT, "h: null handle");
+    if (n_frames > 0 && !x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
+    if (((size_t)x_dev) & 15) return fail(MGX_ERR_ARGUMENT, "x_dev: must be 16-byte aligned");
+    audit_clear(report, bits);
+    const int64_t subs = audit_sub_blocks(n_frames, B);
+    if (n_frames == 0) return audit_gate(nullptr, 0, 0, B, report);
+    MGX_TRY(open_main(h));
+    AuditArgs a;
+    audit_launch(a, n_frames, B, limits->clip_level, limits->silence_level, limits->clip_run);
+    const size_t result_bytes = audit_result_bytes(a);
+    MGX_TRY(ensure(h, h->audit_work, audit_seg_bytes(a) + audit_part_bytes(a)));
+    MGX_TRY(ensure(h, h->audit_out, result_bytes));
+    MGX_TRY(ensure_pinned(h, std::max(result_bytes, (size_t)1 << 16)));
+    a.x = x_dev;
+    a.seg = (AuditSegment*)h->audit_work.p;
+    a.part = (double*)((char*)h->audit_work.p + audit_seg_bytes(a));
+    a.totals = (AuditTotals*)h->audit_out.p;
+    a.sub_sums = (double*)((char*)h->audit_out.p + sizeof(AuditTotals));
+    const dim3 grid((unsigned)a.segments), block(AUDIT_THREADS);
+    if (bits == 0) hipLaunchKernelGGL(k_audit<0>, grid, block, 0, h->stream, a);
+    else if (bits == 16) hipLaunchKernelGGL(k_audit<16>, grid, block, 0, h->stream, a);
+    else if (bits == 24) hipLaunchKernelGGL(k_audit<24>, grid, block, 0, h->stream, a);
+    else hipLaunchKernelGGL(k_audit<32>, grid, block, 0, h->stream, a);
+    hipLaunchKernelGGL(k_audit_merge<0>, dim3(1), dim3(AUDIT_MERGE_THREADS), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->pinned, h->audit_out.p, result_bytes, hipMemcpyDeviceToHost, h->stream));
+    MGX_TRY(sync_main(h));
+    MGX_TRY(check_device_error(h));
+    const AuditTotals* t = (const AuditTotals*)h->pinned;
+    const double* sums = (const double*)((const char*)h->pinned + sizeof(AuditTotals));
+    for (int c = 0; c < 2; ++c) {
+        report->sum[c] = t->sum[c], report->sumsq[c] = t->sumsq[c], report->peak[c] = t->peak[c];
+        report->nonfinite[c] = t->nonfinite[c];
+        report->clip_events[c] = t->clip_events[c], report->clip_samples[c] = t->clip_samples[c];
+        report->clip_longest[c] = t->clip_longest[c], report->clip_first[c] = t->clip_first[c];
+    }
+    report->sum_lr = t->sum_lr;
+    report->head_silence = t->head_silence, report->tail_silence = t->tail_silence;
+    report->gap_longest = t->gap_longest, report->gap_at = t->gap_at;
+    if (sub_sums) std::memcpy(sub_sums, sums, (size_t)subs * 3 * sizeof(double));
+    return audit_gate(sums, subs, n_frames, B, report);
 }
 
 int mgx_window_energy(mgx_handle* h, const float* x_dev, int64_t n, int64_t size, int64_t step, double* energy,

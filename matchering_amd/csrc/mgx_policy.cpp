@@ -117,6 +117,68 @@ int loudness_request(const mgx_loudness_report* report, int64_t n, int32_t sampl
     return 0;
 }
 
+int audit_request(const mgx_audit_limits* limits, const mgx_audit_report* report, int64_t n_frames, int32_t bits,
+                  int32_t sample_rate, const double* sub_sums, int64_t capacity, int64_t* count, int* B) {
+    if (!limits) return fail(MGX_ERR_ARGUMENT, "limits: null");
+    if (!report) return fail(MGX_ERR_ARGUMENT, "report: null");
+    if (n_frames < 0) return fail(MGX_ERR_ARGUMENT, "n_frames: negative");
+    if (bits != 0 && bits != 16 && bits != 24 && bits != 32)
+        return fail(MGX_ERR_ARGUMENT, "bits: the audit reads float32 (0) or 16, 24 or 32-bit PCM");
+    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "sample_rate: the audit's sub-blocks are the meter's, at 8000 Hz and above");
+    if (!std::isfinite(limits->clip_level) || limits->clip_level <= 0.0)
+        return fail(MGX_ERR_ARGUMENT, "clip_level: must be finite and positive");
+    if (limits->clip_run < 1) return fail(MGX_ERR_ARGUMENT, "clip_run: must be at least 1");
+    if (!std::isfinite(limits->silence_level) || limits->silence_level < 0.0)
+        return fail(MGX_ERR_ARGUMENT, "silence_level: must be finite and not negative");
+    if (n_frames > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_audit: tracks of more than 500 million frames are not audited here");
+    *B = (sample_rate + 5) / 10;
+    const int64_t subs = (n_frames + *B - 1) / *B;
+    if (count) *count = subs;
+    if (sub_sums && capacity < subs) return fail(MGX_ERR_ARGUMENT, "capacity: the array holds fewer sub-blocks than the track has");
+    return 0;
+}
+
+void audit_clear(mgx_audit_report* report, int32_t bits) {
+    std::memset(report, 0, sizeof(*report));
+    report->bits = bits;
+    report->clip_first[0] = report->clip_first[1] = -1;
+    report->gap_at = -1;
+    report->correlation_min_at = -1;
+}
+
+int audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int B, mgx_audit_report* report) {
+    report->frames = n_frames;
+    report->sub_blocks = count;
+    report->sub_block_frames = B;
+    const double n = (double)n_frames, ll = report->sumsq[0], rr = report->sumsq[1], lr = report->sum_lr;
+    for (int c = 0; c < 2; ++c) {
+        report->dc[c] = n_frames > 0 ? report->sum[c] / n : NAN;
+        report->rms[c] = n_frames > 0 ? std::sqrt(report->sumsq[c] / n) : NAN;
+    }
+    report->balance_db = rr != 0.0 ? 10.0 * std::log10(ll / rr) : NAN;
+    const double both = std::sqrt(ll * rr);
+    report->correlation = both != 0.0 ? lr / both : NAN;
+    const double power = 2.0 * (ll + rr), mono = ll + rr + 2.0 * lr;
+    report->mono_loss_db = power != 0.0 ? 10.0 * std::log10(mono > 0.0 ? mono / power : 0.0) : NAN;
+    // the correlation of every window of AUDIT_GATE_WINDOW sub-blocks; a shorter track is one window
+    constexpr int64_t AUDIT_GATE_WINDOW = 30;
+    const int64_t width = std::min(count, AUDIT_GATE_WINDOW), windows = count > 0 ? count - width + 1 : 0;
+    double least = NAN;
+    int64_t least_at = -1;
+    for (int64_t k = 0; k < windows; ++k) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int64_t j = 0; j < width; ++j)
+            for (int c = 0; c < 3; ++c) s[c] += sub_sums[(k + j) * 3 + c];
+        const int64_t frames = std::min(n_frames, (k + width) * (int64_t)B) - k * (int64_t)B;
+        if (!((s[0] + s[1]) / (2.0 * (double)frames) >= 1e-7) || s[0] == 0.0 || s[1] == 0.0) continue;
+        const double r = s[2] / std::sqrt(s[0] * s[1]);
+        if (least_at < 0 ? !std::isnan(r) : r < least) least = r, least_at = k;
+    }
+    report->correlation_min = least;
+    report->correlation_min_at = least_at;
+    return 0;
+}
+
 int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither) {
     MGX_TRY(deliver_format_check(bits, dither));
     if (samples < 0) return fail(MGX_ERR_ARGUMENT, "samples: negative");
@@ -362,6 +424,19 @@ int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_ra
     const int S = (sample_rate + 5) / 10;
     loudness_fill(loudness_gate(sub_energy, count, S), count, S, report);
     return 0;
+}
+
+int mgx_audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int32_t sample_rate, mgx_audit_report* report) {
+    if (!report) return fail(MGX_ERR_ARGUMENT, "report: null");
+    if (count < 0) return fail(MGX_ERR_ARGUMENT, "count: negative");
+    if (n_frames < 0) return fail(MGX_ERR_ARGUMENT, "n_frames: negative");
+    if (count > 0 && !sub_sums) return fail(MGX_ERR_ARGUMENT, "sub_sums: null");
+    if (sample_rate < LOUD_MIN_RATE) return fail(MGX_ERR_ARGUMENT, "sample_rate: the audit's sub-blocks are the meter's, at 8000 Hz and above");
+    const int B = (sample_rate + 5) / 10;
+    if (count != (n_frames + B - 1) / B)
+        return fail(MGX_ERR_ARGUMENT, "count: " + std::to_string(n_frames) + " frames are " + std::to_string((n_frames + B - 1) / B) +
+                                      " sub-blocks of " + std::to_string(B) + ", not " + std::to_string(count));
+    return audit_gate(sub_sums, count, n_frames, B, report);
 }
 
 // mgx_delivery_gain (shaper null) and mgx_delivery_gain_shaped

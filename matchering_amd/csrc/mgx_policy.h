@@ -1,6 +1,6 @@
 // The part of libmgx.so that touches no device (mgx_policy.cpp): the calling thread's error text, the validation of a
 // Config, the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
-// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
+// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_audit_gate, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
 // mgx_noise_shaper_preset, mgx_profile_bytes, mgx_eq_shape_check, mgx_shape_fir --
 // and what the device entry points settle from their numbers alone before they touch a handle.
 // No HIP here: g++ compiles the unit by itself (tests/emu/emu_policy_driver.cpp runs it under the sanitizers), and
@@ -43,6 +43,13 @@ int resample_request(const char* entry, const char* subject, const int32_t* chan
                      int32_t rate_out, ResampleGeometry* g, int64_t* n_out);
 int loudness_request(const mgx_loudness_report* report, int64_t n, int32_t sample_rate, const double* sub_energy,
                      int64_t capacity, int64_t* count, int* S);
+// mgx_audit: audit_request writes *count (where given) and *B, the frames of a sub-block, once the numbers are accepted;
+// audit_clear leaves the report of a track without frames (zero counts and sums, positions -1); audit_gate is
+// mgx_audit_gate behind its argument checks: the derived figures from the report's sums and `count` sub-block sums
+int audit_request(const mgx_audit_limits* limits, const mgx_audit_report* report, int64_t n_frames, int32_t bits,
+                  int32_t sample_rate, const double* sub_sums, int64_t capacity, int64_t* count, int* B);
+void audit_clear(mgx_audit_report* report, int32_t bits);
+int audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int B, mgx_audit_report* report);
 int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither);
 // a shaper as every entry point that takes one accepts it, and mgx_deliver_shaped's numbers
 int shaper_check(const mgx_noise_shaper* shaper);

@@ -438,6 +438,26 @@ class Device:
         value = from_report(report, rate, frames)
         return (value, energy) if sub_energy else value
 
+    def audit(self, buf, frames, rate, bits=0, limits=None, sub_sums=False):
+        """The quality-control pass over (frames, 2) samples in HBM at ``rate`` Hz (``mgx_audit``): float32 frames
+        (``bits`` 0) or the integer PCM of a file (16, 24 packed, 32).  ``limits``: a ``qc.AuditLimits``, default its
+        defaults.  Returns a ``qc.Audit``; with ``sub_sums=True`` also the (sub-blocks, 3) sums of L^2, R^2 and L R."""
+        from .qc import AuditLimits, from_report
+
+        limits = AuditLimits() if limits is None else limits
+        report, got = _native.MgxAuditReport(), ctypes.c_int64()
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        block = (int(rate) + 5) // 10
+        capacity = -(-int(frames) // block) if sub_sums and block > 0 and frames > 0 else 0
+        sums = np.zeros((capacity, 3)) if sub_sums else None
+        check(library().mgx_audit(self.handle, ctypes.c_void_p(ptr), int(frames), int(bits), int(rate),
+                                  ctypes.byref(limits.native()), ctypes.byref(report),
+                                  None if sums is None else sums.ctypes.data_as(_native.c_double_p), capacity,
+                                  ctypes.byref(got)))
+        self._keep_until_sync.clear()          # (the call has waited for the stream: the uploads queued before it are done)
+        value = from_report(report, rate)
+        return (value, sums) if sub_sums else value
+
     def download_pcm(self, buf, frames, channels, bits, wait=True):
         """float32 frames in HBM -> integer PCM on the host (pinned): int16 / int32 (n, channels), or uint8
         (n, channels * 3) for packed 24-bit.  Quantised on the device as libsndfile would on the host."""
@@ -453,11 +473,12 @@ class Device:
             self.synchronize()
         return out
 
-    def deliver(self, buf, frames, channels, gain, bits, dither=0, seed=0, wait=True):
+    def deliver(self, buf, frames, channels, gain, bits, dither=0, seed=0, wait=True, inspect=None):
         """float32 frames in HBM -> a delivery rendition on the host (pinned), in one pass on the device
         (``mgx_deliver``): every sample times ``gain``, dithered (0 none, 1 TPDF, 2 high-passed TPDF, keyed by ``seed``),
         quantised and packed -- int16 / int32 (n, channels), uint8 (n, channels * 3) for packed 24-bit, or float32
-        (n, channels) for ``bits`` 0."""
+        (n, channels) for ``bits`` 0.  ``inspect``: called with the DeviceBuffer the kernel wrote, before it is
+        downloaded (the audit of the file as written)."""
         samples = int(frames) * int(channels)
         nbytes = samples * (bits // 8 if bits else 4)
         out_dev = DeviceBuffer(self, max(nbytes, 1))
@@ -465,6 +486,8 @@ class Device:
         try:
             check(library().mgx_deliver(self.handle, ctypes.c_void_p(ptr), samples, float(gain), int(bits), int(dither),
                                         int(seed), ctypes.c_void_p(out_dev.ptr)))
+            if inspect is not None:
+                inspect(out_dev)
             shape, dtype = {0: ((frames, channels), np.float32), 16: ((frames, channels), np.int16),
                             32: ((frames, channels), np.int32), 24: ((frames, channels * 3), np.uint8)}[int(bits)]
             out = self.download(out_dev, shape, dtype, wait=False)
@@ -474,17 +497,19 @@ class Device:
             self.synchronize()
         return out
 
-    def deliver_shaped(self, buf, frames, gain, bits, shaper, seed=0, wait=True):
+    def deliver_shaped(self, buf, frames, gain, bits, shaper, seed=0, wait=True, inspect=None):
         """(frames, 2) float32 in HBM -> a noise-shaped 16 or 24-bit rendition on the host (pinned), in one launch
         (``mgx_deliver_shaped``): every sample times ``gain``, TPDF-dithered (keyed by ``seed``), quantised with the error
         fed back through ``shaper`` (a ``delivery.NoiseShaper``) and packed -- int16 (n, 2), or uint8 (n, 6) for packed
-        24-bit."""
+        24-bit.  ``inspect``: as ``deliver``'s."""
         nbytes = int(frames) * 2 * (int(bits) // 8)
         out_dev = DeviceBuffer(self, max(nbytes, 1))
         ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
         try:
             check(library().mgx_deliver_shaped(self.handle, ctypes.c_void_p(ptr), int(frames), float(gain), int(bits),
                                                ctypes.byref(shaper.native()), int(seed), ctypes.c_void_p(out_dev.ptr)))
+            if inspect is not None:
+                inspect(out_dev)
             shape, dtype = {16: ((frames, 2), np.int16), 24: ((frames, 6), np.uint8)}[int(bits)]
             out = self.download(out_dev, shape, dtype, wait=False)
         finally:

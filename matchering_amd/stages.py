@@ -77,7 +77,7 @@ def _limited(dev, rendering, n, rate, delivery, bits, measured):
 
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
-         encodings=None, preview=None, loudness=None, deliveries=None, eq=None):
+         encodings=None, preview=None, loudness=None, deliveries=None, eq=None, audit=None):
     # (``device``: the handle to run on, default the process-wide one; ``fir``: a DeviceBuffer with a
     # matching FIR to apply instead of designing one -- batch.master_album; ``encodings``: per output,
     # None for float32 frames or "PCM_16" / "PCM_24" / "PCM_32" for the integer samples a file of that
@@ -99,7 +99,11 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # delivery at another ``sample_rate`` than the internal one is made from the rendering converted to that rate in HBM
     # (mgx_convert_rate) and measured there; the renderings returned, the previews and the other callbacks do not change.
     # ``eq``: an eq.MatchingEq (or its JSON object) -- how much of the matching curve is applied, its boost and cut
-    # caps, the FIR's phase (mgx_master_shaped); None: the reference's FIR.  A given ``fir`` is used as given.)
+    # caps, the FIR's phase (mgx_master_shaped); None: the reference's FIR.  A given ``fir`` is used as given.
+    # ``audit``: a callable that receives (name, qc.Audit) for the names ``loudness`` receives -- the quality-control pass
+    # (mgx_audit) over the float frames in HBM -- and for "delivered:" + key the audit of the buffer mgx_deliver /
+    # mgx_deliver_shaped wrote, at the delivery's own rate and width, before it is downloaded: the file as written.  None:
+    # nothing is launched.)
     from .eq import as_eq
 
     eq = as_eq(eq)
@@ -172,6 +176,13 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                     if returned[slot]:
                         metered[slot] = dev.loudness(outs[slot], n, rate)
                         loudness(name, metered[slot])
+            if audit is not None:
+                audit("target", dev.audit(t_dev, n, rate))
+                if r_dev is not None:
+                    audit("reference", dev.audit(r_dev, nr, rate))
+                for slot, name in enumerate(("result", "result_no_limiter", "result_no_limiter_normalized")):
+                    if returned[slot]:
+                        audit(name, dev.audit(outs[slot], n, rate))
             if deliveries:
                 from dataclasses import replace
 
@@ -205,13 +216,17 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                         record = replace(record, sample_rate=out_rate, frames=length, internal_rate=rate)
                         deliveries.delivered[key] = record
                         # queued behind the measurement; the array is valid after the one wait below
+                        written = {}
+                        if audit is not None:            # the buffer the kernel wrote, audited before it is downloaded
+                            written["inspect"] = lambda b, k=key, m=length, r=out_rate, w=bits: audit(
+                                "delivered:" + str(k), dev.audit(b, m, r, w))
                         try:
                             if delivery.shaped:          # (the policy above was the _shaped one: delivery.delivery_gain)
                                 deliveries.arrays[key] = dev.deliver_shaped(frames, length, record.gain, bits, delivery.shaper,
-                                                                            delivery.seed, wait=False)
+                                                                            delivery.seed, wait=False, **written)
                             else:
                                 deliveries.arrays[key] = dev.deliver(frames, length, 2, record.gain, bits,
-                                                                     DITHERS[delivery.dither], delivery.seed, wait=False)
+                                                                     DITHERS[delivery.dither], delivery.seed, wait=False, **written)
                         finally:
                             if limited is not None:
                                 frames.release() # (recycled by later work on this stream only, which is ordered behind the kernel)
