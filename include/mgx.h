@@ -615,6 +615,58 @@ int mgx_audit(mgx_handle* h, const void* x_dev, int64_t n_frames, int32_t bits, 
               int64_t* count);
 int mgx_audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int32_t sample_rate, mgx_audit_report* report);
 
+/* Visuals: the pictures a mastering front end shows -- a waveform overview and a spectrogram -- computed from (n, 2)
+ * float32 frames while they are in HBM; what comes back is a few hundred kilobytes (the reference has nothing of the
+ * kind; a caller would download every frame and transform on the host).  Part of the new surface, like the meter and the
+ * audit.  DESIGN.md section 3.18.
+ * (V1) Overview.  W columns, 1 <= W <= min(n, 65536).  Column c covers frames [floor(c n / W), floor((c + 1) n / W)),
+ *   in 64-bit arithmetic.  Per column and channel: the smallest and the largest sample, as the float32 values
+ *   themselves, and the float64 sum of squares (a float32 square is exact in float64).  A NaN is skipped by the minimum
+ *   and the maximum (fminf / fmaxf from +inf / -inf, as numpy's fmin / fmax) and enters the sum as it is.
+ * (V2) Spectrogram.
+ *   parameters: N = 2^log2_fft, log2_fft in 8..14; hop H, 1 <= H <= N; W columns; channels 0 (left, right) or 1 (mid,
+ *     side exactly as the analysis forms them: m = (L + R) * 0.5f, s = m - R, in float32); B bands, edges[0..B].
+ *   window: periodic Hann, w[i] = 0.5 - 0.5 cos(2 pi i / N), computed in float64 and rounded to float32; sum w is the
+ *     float64 sum of those float32 values.
+ *   hops: centred.  Hop t is frames [t H - N/2, t H + N/2), frames outside the track being zero; T = floor((n - 1) / H) + 1.
+ *   power: per hop and channel P_t[k] = |X_t[k]|^2 (2 / sum w)^2, k = 0 .. N/2, X the N-point DFT of the windowed hop:
+ *     a full-scale sine on a bin centre reads 1.0.  DC and Nyquist are NOT treated specially: having no mirror bin they
+ *     read four times what the convention of a real tone would give them.
+ *   time pooling: with 1 <= W <= T, column c is the mean of P_t over t in [floor(c T / W), floor((c + 1) T / W));
+ *     columns == 0 means W = T; W = 1 is the long-term average spectrum.
+ *   frequency pooling: band b is the mean of bins [edges[b], edges[b + 1]); edges strictly ascending, edges[0] >= 0,
+ *     edges[B] <= N/2 + 1.  edges = 0, 1, .., N/2 + 1 gives every bin.
+ *   output: linear power, float32, [W][2][B] (column, channel, band), on the host.  Decibels are the caller's.
+ * (V3) Empty input: n == 0 gives zero hops and zero columns, launches nothing and returns 0, as mgx_audit does.
+ * (V4) Limits: more than 500 million frames is MGX_ERR_UNSUPPORTED; so is a spectrogram whose partial spectra
+ *   (W ceil(ceil(T / W) / 32) (N + 2) floats) or whose picture (2 W B floats) exceed 2 GiB -- it asks for fewer columns.
+ *   Every other bad argument is MGX_ERR_ARGUMENT; mgx_last_error names the field and the offending value.
+ * mgx_spectrogram_plan needs no device: it makes every refusal of (V2) and (V4) that depends on the numbers alone and
+ * returns T in *hops and W in *columns (either may be NULL).
+ * mgx_spectrogram: two launches on the handle's stream (csrc/visuals_kernel.h: k_spectrogram<log2_fft>, a workgroup per
+ * run of at most 32 consecutive hops of one column, accumulated in float32 in hop order; k_spectro_pool, which adds a
+ * column's runs in order and a band's bins in float64), none of whose workgroups waits for another; no atomics: two calls
+ * on the same input give the same bits.  It waits for the result (as mgx_loudness does).  `power` (host) receives
+ * [W][2][B] floats, `capacity` is the number of floats it holds, *count (may be NULL) receives W.  Beyond the plan's
+ * refusals: a null h, power or (n > 0) x_dev; x_dev not 8-byte aligned; capacity below 2 W B.
+ * mgx_overview: two launches (k_overview, a workgroup per 16384 frames of a column; k_overview_fold, which folds a
+ * column's shares in order), waits.  minmax (host) receives [W][2][2] = column, channel, {smallest, largest}; sumsq
+ * [W][2].  Refusals as (V1), (V4): a null h, minmax, sumsq or (n > 0) x_dev, a misaligned x_dev, n negative, columns
+ * outside 1 .. min(n, 65536) (V3 first: with n == 0 the columns are not looked at). */
+typedef struct mgx_spectrogram_spec {
+    int32_t log2_fft;
+    int32_t hop;
+    int32_t columns;                     /* 0: one per hop */
+    int32_t channels;                    /* 0: left / right, 1: mid / side */
+    int32_t bands;
+} mgx_spectrogram_spec;
+int mgx_spectrogram_plan(int64_t n_frames, const mgx_spectrogram_spec* spec, const int32_t* edges, int64_t* hops,
+                         int32_t* columns);
+int mgx_spectrogram(mgx_handle* h, const float* x_dev, int64_t n_frames, const mgx_spectrogram_spec* spec,
+                    const int32_t* edges, float* power, int64_t capacity, int64_t* count);
+int mgx_overview(mgx_handle* h, const float* x_dev, int64_t n_frames, int32_t columns, float* minmax /* [W][2][2] */,
+                 double* sumsq /* [W][2] */);
+
 /* A/B previews (matchering/preview_creator.py:30-94) on frames that are still in HBM.
  * mgx_window_energy: dsp.py:128-143 (strided_app_2d + batch_rms_2d): sum of squares over both channels of
  * every window of `size` frames taken every `step` frames (`size` > n: the whole track is the one window);

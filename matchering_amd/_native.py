@@ -145,6 +145,18 @@ class MgxAuditReport(ctypes.Structure):
     ]
 
 
+class MgxSpectrogramSpec(ctypes.Structure):
+    """mgx_spectrogram_spec (include/mgx.h)."""
+
+    _fields_ = [
+        ("log2_fft", ctypes.c_int32),
+        ("hop", ctypes.c_int32),
+        ("columns", ctypes.c_int32),
+        ("channels", ctypes.c_int32),
+        ("bands", ctypes.c_int32),
+    ]
+
+
 class MgxDelivery(ctypes.Structure):
     """mgx_delivery (include/mgx.h)."""
 
@@ -279,6 +291,11 @@ SYMBOLS = {
                                  ctypes.POINTER(MgxAuditReport), c_double_p, ctypes.c_int64, c_int64_p]),
     "mgx_audit_gate": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(MgxAuditReport)]),
+    "mgx_spectrogram_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(MgxSpectrogramSpec), ctypes.POINTER(ctypes.c_int32),
+                                            c_int64_p, ctypes.POINTER(ctypes.c_int32)]),
+    "mgx_spectrogram": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxSpectrogramSpec),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.c_int64, c_int64_p]),
+    "mgx_overview": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), c_double_p]),
     "mgx_delivery_gain": (ctypes.c_int, [ctypes.POINTER(MgxDelivery), ctypes.POINTER(MgxLoudnessReport),
                                          ctypes.POINTER(MgxDeliveryResult)]),
     "mgx_deliver": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,

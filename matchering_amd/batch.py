@@ -36,7 +36,9 @@ optional: ``delivery.Delivery``; ``"dither"``: a name -- "lipshitz5" and "wannam
 list of audio files and saved profiles that are merged into one profile (``ReferenceProfile.merge``).  A job may carry
 ``"eq": {"amount": 0.5, "max_boost_db": 6, "max_cut_db": 6, "phase": "minimum"}`` (every key optional:
 ``eq.MatchingEq``), the controls of its matching EQ, and ``"audit": true``: its tracks, renderings and deliveries are
-audited (``qc.audit``) and the job carries the audits as plain dicts under ``"audit"`` afterwards.
+audited (``qc.audit``) and the job carries the audits as plain dicts under ``"audit"`` afterwards; and
+``"visuals": true`` or ``{"columns": 512, "bands": 64, ...}`` (``visuals.VisualsRequest``): the waveform overview and the
+spectrogram of its tracks and renderings are made in HBM and the job carries them as plain dicts under ``"visuals"``.
 """
 
 import json
@@ -263,26 +265,29 @@ def _device_worker(device_index, lane, config, needs, master, encodings=None):
     """A callable mastering one (target, reference) array pair on the lane's own device handle.
     ``encodings``: stages.main's (integer PCM renderings straight from the GPU).  ``deliveries`` (per call): a job's
     ``delivery.DeliveryRequest``, handed to ``main`` where the job has one; ``eq`` (per call): the job's
-    ``eq.MatchingEq``, likewise; ``audit`` (per call): ``stages.main``'s handler, where the job asks for audits."""
-    def extra(deliveries, eq, audit):
+    ``eq.MatchingEq``, likewise; ``audit`` (per call): ``stages.main``'s handler, where the job asks for audits;
+    ``visuals`` (per call): the same for its pictures."""
+    def extra(deliveries, eq, audit, visuals=None):
         given = {"deliveries": deliveries} if deliveries else {}
         if eq is not None:
             given["eq"] = eq
         if audit is not None:
             given["audit"] = audit
+        if visuals is not None:
+            given["visuals"] = visuals
         return given
 
     if master is not None:                         # tests inject a stand-in for the GPU
         if encodings is None or not any(encodings):
-            return lambda pair, deliveries=None, eq=None, audit=None: master(pair[0], pair[1], config, *needs,
-                                                                             **extra(deliveries, eq, audit))
-        return lambda pair, deliveries=None, eq=None, audit=None: master(pair[0], pair[1], config, *needs, encodings=encodings,
-                                                                         **extra(deliveries, eq, audit))
+            return lambda pair, deliveries=None, eq=None, audit=None, visuals=None: master(pair[0], pair[1], config, *needs,
+                                                                             **extra(deliveries, eq, audit, visuals))
+        return lambda pair, deliveries=None, eq=None, audit=None, visuals=None: master(pair[0], pair[1], config, *needs, encodings=encodings,
+                                                                         **extra(deliveries, eq, audit, visuals))
     from .stages import main
 
     dev = lane_device(device_index, lane)
-    return lambda pair, deliveries=None, eq=None, audit=None: main(pair[0], pair[1], config, *needs, device=dev,
-                                                                   encodings=encodings, **extra(deliveries, eq, audit))
+    return lambda pair, deliveries=None, eq=None, audit=None, visuals=None: main(pair[0], pair[1], config, *needs, device=dev,
+                                                                   encodings=encodings, **extra(deliveries, eq, audit, visuals))
 
 
 def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
@@ -580,6 +585,13 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                     # "audit": true -> the job's audits as plain dicts, by the names stages.main's handler receives
                     audits = jobs[index]["audit"] = {}
                     shaped["audit"] = lambda name, value, kept=audits: kept.__setitem__(name, value.as_dict())
+                if jobs[index].get("visuals"):
+                    # "visuals": true or the sizes -> the job's pictures as plain dicts, by the same names
+                    from .visuals import VisualsRequest
+
+                    pictures, sizes = {}, VisualsRequest.from_json(jobs[index]["visuals"])
+                    jobs[index]["visuals"] = pictures
+                    shaped["visuals"] = (lambda name, value, kept=pictures: kept.__setitem__(name, value.as_dict()), sizes)
                 if not deliveries:
                     return workers[key]((target, reference), **shaped)
                 return _WithDeliveries(workers[key]((target, reference), deliveries, **shaped), deliveries)
@@ -640,6 +652,8 @@ def jobs_from_json(path):
         job = {"target": item["target"], "results": results}
         if item.get("audit"):
             job["audit"] = True
+        if item.get("visuals"):
+            job["visuals"] = item["visuals"]
         if item.get("eq") is not None:
             from .eq import MatchingEq
 

@@ -58,14 +58,18 @@ def _same_file(a, b):
 
 
 def process(target: str, reference: str, results: list, config: Config = None,
-            preview_target: Result = None, preview_result: Result = None, loudness=None, eq=None, audit=None):
+            preview_target: Result = None, preview_result: Result = None, loudness=None, eq=None, audit=None,
+            visuals=None):
     # (``loudness``: no counterpart in the reference -- a callable that receives (name, loudness.Loudness) for "target",
     # for "reference" when its audio was loaded, and for each rendering the results need ("result", "result_no_limiter",
     # "result_no_limiter_normalized"), measured on the frames in HBM; None: nothing is measured, nothing else changes.
     # ``eq``: an eq.MatchingEq -- how much of the matching curve is applied, its boost and cut caps, the phase of the FIR;
     # None: the reference's FIR.  What the library refuses is a ValueError before a file is read.
     # ``audit``: a callable that receives (name, qc.Audit) for the same names, and for "delivered:" + file the audit of the
-    # integer samples a delivery writes, read in HBM before they are downloaded; None: nothing is launched.)
+    # integer samples a delivery writes, read in HBM before they are downloaded; None: nothing is launched.
+    # ``visuals``: a callable, or a pair (callable, visuals.VisualsRequest) giving the sizes, that receives (name,
+    # visuals.Visuals) -- waveform overview and spectrogram of the frames in HBM -- for "target", "reference" and each
+    # rendering; None: nothing is launched.)
     from .eq import as_eq
 
     config = Config() if config is None else config
@@ -114,6 +118,8 @@ def process(target: str, reference: str, results: list, config: Config = None,
         extra["eq"] = eq
     if audit is not None:
         extra["audit"] = audit
+    if visuals is not None:
+        extra["visuals"] = visuals
     # (main releases the resident frames)
     renderings = main(target_track.for_main, reference_audio, config, *needs, encodings=encodings, **extra)
     del reference_audio

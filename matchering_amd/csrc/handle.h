@@ -166,6 +166,14 @@ struct mgx_handle {
     DevBuf loudness_out;                    // [nsub][2] sub-block energies, then [workgroups][2] peaks
     DevBuf tp_plane, tp_words;              // mgx_tp_limit: the d0 plane [tiles * T] float32; aggregates and peaks, [2][tiles] float64
     DevBuf audit_work, audit_out;           // mgx_audit: the segments' records and sub-block shares; the totals, then [count][3] sub-block sums
+    // mgx_spectrogram: the float32 window of every transform length this handle has drawn, built once per log2, and the
+    // float64 sum of its values
+    struct SpectroWindow {
+        DevBuf table;
+        double sum = 0.0;
+    };
+    std::map<int, SpectroWindow> spectro_windows;
+    DevBuf visuals_work, visuals_out;       // mgx_spectrogram / mgx_overview: the workgroups' partials (then the band edges); the picture
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
     // set by a kernel whose bounded wait expired (limiter look-back, level-correction round): one word of

@@ -31,6 +31,7 @@
 #include "tp_limit_kernel.h"
 #include "deliver_shaped_kernel.h"
 #include "audit_kernel.h"
+#include "visuals_kernel.h"
 
 #include "mgx_policy.h"
 #include "handle.h"
@@ -40,6 +41,7 @@
 #include "run_limiter.h"               // (ahead of the correction: its round 0 presets the limiter's look-back words)
 #include "run_correction.h"
 #include "device_errors.h"
+#include "run_visuals.h"
 #include "master_call.h"
 
 #define NCCL_TRY(expr)                                                                       \
@@ -493,6 +495,89 @@ int mgx_audit(mgx_handle* h, const void* x_dev, int64_t n_frames, int32_t bits, 
     report->gap_longest = t->gap_longest, report->gap_at = t->gap_at;
     if (sub_sums) std::memcpy(sub_sums, sums, (size_t)subs * 3 * sizeof(double));
     return audit_gate(sums, subs, n_frames, B, report);
+}
+
+int mgx_spectrogram(mgx_handle* h, const float* x_dev, int64_t n_frames, const mgx_spectrogram_spec* spec,
+                    const int32_t* edges, float* power, int64_t capacity, int64_t* count) {
+    // everything that depends on the numbers alone is settled before the handle is touched
+    SpectroPlan plan;
+    MGX_TRY(spectrogram_request(n_frames, spec, edges, &plan));
+    if (!h) return fail(MGX_ERR_ARGUMENT, "h: null handle");
+    if (n_frames > 0 && !x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
+    if (((size_t)x_dev) & 7) return fail(MGX_ERR_ARGUMENT, "x_dev: must be 8-byte aligned");
+    if (count) *count = plan.columns;
+    if (n_frames == 0) return 0;
+    const long long values = (long long)plan.columns * 2 * spec->bands;
+    if (!power) return fail(MGX_ERR_ARGUMENT, "power: null");
+    if (capacity < values)
+        return fail(MGX_ERR_ARGUMENT, "capacity: " + std::to_string(capacity) + " floats hold fewer than the picture's " +
+                                          std::to_string(values));
+    MGX_TRY(open_main(h));
+    const int N = 1 << spec->log2_fft, half = N / 2;
+    mgx_handle::SpectroWindow* window = nullptr;
+    MGX_TRY(spectro_window(h, spec->log2_fft, &window));
+    SpectroArgs a;
+    a.x = reinterpret_cast<const float2*>(x_dev);
+    a.n = n_frames;
+    a.hop = spec->hop, a.hops = plan.hops, a.columns = plan.columns, a.parts = plan.parts;
+    a.channels = spec->channels, a.bands = spec->bands;
+    a.window = (const float*)window->table.p;
+    MGX_TRY(get_twiddles(h, spec->log2_fft, &a.tw));
+    const size_t part_bytes = (size_t)plan.columns * plan.parts * 2 * (half + 1) * sizeof(float);
+    const size_t edge_bytes = (size_t)(spec->bands + 1) * sizeof(int);
+    MGX_TRY(ensure(h, h->visuals_work, part_bytes + edge_bytes));
+    MGX_TRY(ensure(h, h->visuals_out, (size_t)values * sizeof(float)));
+    a.part = (float*)h->visuals_work.p;
+    a.edges = (const int*)((char*)h->visuals_work.p + part_bytes);
+    a.scale = (2.0 / window->sum) * (2.0 / window->sum) * 0.25;
+    a.out = (float*)h->visuals_out.p;
+    HIP_TRY(hipMemcpyAsync((void*)a.edges, edges, edge_bytes, hipMemcpyHostToDevice, h->stream));
+    switch (spec->log2_fft) {
+#define CASE(L) case L: MGX_TRY(launch_spectrogram<L>(h, a)); break;
+        CASE(8) CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14)
+#undef CASE
+        default: return fail(MGX_ERR_ARGUMENT, "log2_fft: outside 8 .. 14");
+    }
+    hipLaunchKernelGGL(k_spectro_pool<0>, dim3((unsigned)((values + 255) / 256)), dim3(256), 0, h->stream, a, half);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(power, a.out, (size_t)values * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    MGX_TRY(sync_main(h));
+    MGX_TRY(check_device_error(h));
+    return 0;
+}
+
+int mgx_overview(mgx_handle* h, const float* x_dev, int64_t n_frames, int32_t columns, float* minmax, double* sumsq) {
+    int parts = 0;
+    MGX_TRY(overview_request(n_frames, columns, &parts));
+    if (!h) return fail(MGX_ERR_ARGUMENT, "h: null handle");
+    if (n_frames > 0 && !x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
+    if (((size_t)x_dev) & 7) return fail(MGX_ERR_ARGUMENT, "x_dev: must be 8-byte aligned");
+    if (n_frames == 0) return 0;
+    if (!minmax) return fail(MGX_ERR_ARGUMENT, "minmax: null");
+    if (!sumsq) return fail(MGX_ERR_ARGUMENT, "sumsq: null");
+    MGX_TRY(open_main(h));
+    OverviewArgs a;
+    a.x = reinterpret_cast<const float2*>(x_dev);
+    a.n = n_frames, a.columns = columns, a.parts = parts;
+    // per (column, share) and channel: a double and two floats; the result the same per (column, channel)
+    const size_t groups = (size_t)columns * parts;
+    MGX_TRY(ensure(h, h->visuals_work, groups * 2 * (sizeof(double) + 2 * sizeof(float))));
+    MGX_TRY(ensure(h, h->visuals_out, (size_t)columns * 2 * (sizeof(double) + 2 * sizeof(float))));
+    MGX_TRY(ensure_pinned(h, std::max((size_t)columns * 2 * (sizeof(double) + 2 * sizeof(float)), (size_t)1 << 16)));
+    a.part_sumsq = (double*)h->visuals_work.p;
+    a.part_minmax = (float*)(a.part_sumsq + groups * 2);
+    a.sumsq = (double*)h->visuals_out.p;
+    a.minmax = (float*)(a.sumsq + (size_t)columns * 2);
+    hipLaunchKernelGGL(k_overview<0>, dim3((unsigned)groups), dim3(OVERVIEW_THREADS), 0, h->stream, a);
+    hipLaunchKernelGGL(k_overview_fold<0>, dim3((unsigned)((columns * 2 + 255) / 256)), dim3(256), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    const size_t result_bytes = (size_t)columns * 2 * (sizeof(double) + 2 * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(h->pinned, h->visuals_out.p, result_bytes, hipMemcpyDeviceToHost, h->stream));
+    MGX_TRY(sync_main(h));
+    MGX_TRY(check_device_error(h));
+    std::memcpy(sumsq, h->pinned, (size_t)columns * 2 * sizeof(double));
+    std::memcpy(minmax, (const char*)h->pinned + (size_t)columns * 2 * sizeof(double), (size_t)columns * 4 * sizeof(float));
+    return 0;
 }
 
 int mgx_window_energy(mgx_handle* h, const float* x_dev, int64_t n, int64_t size, int64_t step, double* energy,

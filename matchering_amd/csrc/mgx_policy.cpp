@@ -179,6 +179,59 @@ int audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int B, m
     return 0;
 }
 
+int spectrogram_request(int64_t n_frames, const mgx_spectrogram_spec* spec, const int32_t* edges, SpectroPlan* plan) {
+    const auto num = [](long long v) { return std::to_string(v); };
+    if (!spec) return fail(MGX_ERR_ARGUMENT, "spec: null");
+    if (!edges) return fail(MGX_ERR_ARGUMENT, "edges: null");
+    if (n_frames < 0) return fail(MGX_ERR_ARGUMENT, "n_frames: " + num(n_frames) + " is negative");
+    if (spec->log2_fft < SPECTRO_LOG2_MIN || spec->log2_fft > SPECTRO_LOG2_MAX)
+        return fail(MGX_ERR_ARGUMENT, "log2_fft: " + num(spec->log2_fft) + " is outside 8 .. 14");
+    const int N = 1 << spec->log2_fft, half = N / 2;
+    if (spec->hop < 1 || spec->hop > N)
+        return fail(MGX_ERR_ARGUMENT, "hop: " + num(spec->hop) + " is outside 1 .. " + num(N));
+    if (spec->channels != 0 && spec->channels != 1)
+        return fail(MGX_ERR_ARGUMENT, "channels: " + num(spec->channels) + " is neither 0 (left / right) nor 1 (mid / side)");
+    if (spec->bands < 1 || spec->bands > half + 1)
+        return fail(MGX_ERR_ARGUMENT, "bands: " + num(spec->bands) + " is outside 1 .. " + num(half + 1));
+    if (edges[0] < 0) return fail(MGX_ERR_ARGUMENT, "edges[0]: " + num(edges[0]) + " is negative");
+    for (int b = 0; b < spec->bands; ++b)
+        if (edges[b + 1] <= edges[b])
+            return fail(MGX_ERR_ARGUMENT, "edges[" + num(b + 1) + "]: " + num(edges[b + 1]) + " does not exceed edges[" +
+                                              num(b) + "] = " + num(edges[b]));
+    if (edges[spec->bands] > half + 1)
+        return fail(MGX_ERR_ARGUMENT, "edges[" + num(spec->bands) + "]: " + num(edges[spec->bands]) + " exceeds the " +
+                                          num(half + 1) + " bins");
+    if (spec->columns < 0) return fail(MGX_ERR_ARGUMENT, "columns: " + num(spec->columns) + " is negative");
+    if (n_frames > VISUALS_FRAMES_MAX)
+        return fail(MGX_ERR_UNSUPPORTED, "n_frames: " + num(n_frames) + " exceeds the 500 million frames a picture is made of");
+    plan->hops = spectro_hops(n_frames, spec->hop);
+    plan->columns = 0, plan->parts = 0;
+    if (n_frames == 0) return 0;
+    if (spec->columns > plan->hops)
+        return fail(MGX_ERR_ARGUMENT, "columns: " + num(spec->columns) + " exceeds the " + num(plan->hops) + " hops");
+    const long long W = spec->columns == 0 ? plan->hops : spec->columns;
+    const long long parts = visuals_parts(plan->hops, (int)std::min<long long>(W, INT_MAX), SPECTRO_RUN_CAP);
+    if (W * parts * (N + 2) * 4 > VISUALS_BYTES_MAX || W * 2 * spec->bands * 4 > VISUALS_BYTES_MAX)
+        return fail(MGX_ERR_UNSUPPORTED, "columns: " + num(W) + " columns of " + num(spec->bands) + " bands at " + num(N) +
+                                             " points exceed 2 GiB of spectra: ask for fewer columns");
+    plan->columns = (int)W, plan->parts = (int)parts;
+    return 0;
+}
+
+int overview_request(int64_t n_frames, int32_t columns, int* parts) {
+    const auto num = [](long long v) { return std::to_string(v); };
+    if (n_frames < 0) return fail(MGX_ERR_ARGUMENT, "n_frames: " + num(n_frames) + " is negative");
+    if (n_frames > VISUALS_FRAMES_MAX)
+        return fail(MGX_ERR_UNSUPPORTED, "n_frames: " + num(n_frames) + " exceeds the 500 million frames a picture is made of");
+    *parts = 0;
+    if (n_frames == 0) return 0;
+    const long long most = std::min<long long>(n_frames, OVERVIEW_COLUMNS_MAX);
+    if (columns < 1 || columns > most)
+        return fail(MGX_ERR_ARGUMENT, "columns: " + num(columns) + " is outside 1 .. " + num(most));
+    *parts = visuals_parts(n_frames, columns, OVERVIEW_SHARE);
+    return 0;
+}
+
 int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither) {
     MGX_TRY(deliver_format_check(bits, dither));
     if (samples < 0) return fail(MGX_ERR_ARGUMENT, "samples: negative");
@@ -437,6 +490,15 @@ int mgx_audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int3
         return fail(MGX_ERR_ARGUMENT, "count: " + std::to_string(n_frames) + " frames are " + std::to_string((n_frames + B - 1) / B) +
                                       " sub-blocks of " + std::to_string(B) + ", not " + std::to_string(count));
     return audit_gate(sub_sums, count, n_frames, B, report);
+}
+
+int mgx_spectrogram_plan(int64_t n_frames, const mgx_spectrogram_spec* spec, const int32_t* edges, int64_t* hops,
+                         int32_t* columns) {
+    SpectroPlan plan;
+    MGX_TRY(spectrogram_request(n_frames, spec, edges, &plan));
+    if (hops) *hops = plan.hops;
+    if (columns) *columns = plan.columns;
+    return 0;
 }
 
 // mgx_delivery_gain (shaper null) and mgx_delivery_gain_shaped

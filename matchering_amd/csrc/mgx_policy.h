@@ -1,6 +1,6 @@
 // The part of libmgx.so that touches no device (mgx_policy.cpp): the calling thread's error text, the validation of a
 // Config, the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
-// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_audit_gate, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
+// mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_audit_gate, mgx_spectrogram_plan, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
 // mgx_noise_shaper_preset, mgx_profile_bytes, mgx_eq_shape_check, mgx_shape_fir --
 // and what the device entry points settle from their numbers alone before they touch a handle.
 // No HIP here: g++ compiles the unit by itself (tests/emu/emu_policy_driver.cpp runs it under the sanitizers), and
@@ -15,6 +15,7 @@
 #include "loudness_plan.h"
 #include "noise_shaper.h"
 #include "resample_plan.h"
+#include "visuals_plan.h"
 
 namespace mgx {
 
@@ -50,6 +51,15 @@ int audit_request(const mgx_audit_limits* limits, const mgx_audit_report* report
                   int32_t sample_rate, const double* sub_sums, int64_t capacity, int64_t* count, int* B);
 void audit_clear(mgx_audit_report* report, int32_t bits);
 int audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int B, mgx_audit_report* report);
+// mgx_spectrogram_plan behind its name: every refusal of a spectrogram that its numbers alone decide, then the hops T,
+// the columns W and the workgroups per column; overview_request the same for mgx_overview (n_frames == 0: accepted, no
+// columns, *parts 0)
+struct SpectroPlan {
+    long long hops;
+    int columns, parts;
+};
+int spectrogram_request(int64_t n_frames, const mgx_spectrogram_spec* spec, const int32_t* edges, SpectroPlan* plan);
+int overview_request(int64_t n_frames, int32_t columns, int* parts);
 int deliver_check(int64_t samples, double gain, int32_t bits, int32_t dither);
 // a shaper as every entry point that takes one accepts it, and mgx_deliver_shaped's numbers
 int shaper_check(const mgx_noise_shaper* shaper);

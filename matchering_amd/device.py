@@ -458,6 +458,38 @@ class Device:
         value = from_report(report, rate)
         return (value, sums) if sub_sums else value
 
+    def overview(self, buf, frames, rate, columns):
+        """The waveform overview of (frames, 2) float32 in HBM (``mgx_overview``): a ``visuals.Overview`` of ``columns``
+        columns."""
+        from .visuals import Overview
+
+        columns = int(columns) if frames > 0 else 0
+        minmax, sumsq = np.zeros((columns, 2, 2), dtype=np.float32), np.zeros((columns, 2))
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        check(library().mgx_overview(self.handle, ctypes.c_void_p(ptr), int(frames), columns,
+                                     minmax.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                     sumsq.ctypes.data_as(_native.c_double_p)))
+        self._keep_until_sync.clear()          # (the call has waited for the stream)
+        return Overview(int(rate), int(frames), minmax[:, :, 0].copy(), minmax[:, :, 1].copy(), sumsq)
+
+    def spectrogram(self, buf, frames, rate, fft_size=4096, hop=1024, columns=0, edges=None, channels="lr"):
+        """The spectrogram of (frames, 2) float32 in HBM (``mgx_spectrogram``): a ``visuals.Spectrogram``.  ``edges``:
+        the bands' bin edges (int32), default every bin."""
+        from . import visuals
+
+        edges = visuals.linear_bands(fft_size) if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+        spec = visuals.spec_of(fft_size, hop, columns, channels, edges)
+        edges_p = edges.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        hops, width = ctypes.c_int64(), ctypes.c_int32()
+        check(library().mgx_spectrogram_plan(int(frames), ctypes.byref(spec), edges_p, ctypes.byref(hops), ctypes.byref(width)))
+        power = np.zeros((width.value, 2, spec.bands), dtype=np.float32)
+        got = ctypes.c_int64()
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        check(library().mgx_spectrogram(self.handle, ctypes.c_void_p(ptr), int(frames), ctypes.byref(spec), edges_p,
+                                        power.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), power.size, ctypes.byref(got)))
+        self._keep_until_sync.clear()
+        return visuals.Spectrogram(int(rate), int(frames), int(fft_size), int(hop), int(hops.value), channels, edges, power)
+
     def download_pcm(self, buf, frames, channels, bits, wait=True):
         """float32 frames in HBM -> integer PCM on the host (pinned): int16 / int32 (n, channels), or uint8
         (n, channels * 3) for packed 24-bit.  Quantised on the device as libsndfile would on the host."""

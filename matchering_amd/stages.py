@@ -77,7 +77,7 @@ def _limited(dev, rendering, n, rate, delivery, bits, measured):
 
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
-         encodings=None, preview=None, loudness=None, deliveries=None, eq=None, audit=None):
+         encodings=None, preview=None, loudness=None, deliveries=None, eq=None, audit=None, visuals=None):
     # (``device``: the handle to run on, default the process-wide one; ``fir``: a DeviceBuffer with a
     # matching FIR to apply instead of designing one -- batch.master_album; ``encodings``: per output,
     # None for float32 frames or "PCM_16" / "PCM_24" / "PCM_32" for the integer samples a file of that
@@ -103,7 +103,10 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # ``audit``: a callable that receives (name, qc.Audit) for the names ``loudness`` receives -- the quality-control pass
     # (mgx_audit) over the float frames in HBM -- and for "delivered:" + key the audit of the buffer mgx_deliver /
     # mgx_deliver_shaped wrote, at the delivery's own rate and width, before it is downloaded: the file as written.  None:
-    # nothing is launched.)
+    # nothing is launched.
+    # ``visuals``: a callable, or a pair (callable, visuals.VisualsRequest) giving the sizes, that receives (name,
+    # visuals.Visuals) -- the waveform overview and the spectrogram (mgx_overview, mgx_spectrogram) of the float frames
+    # in HBM -- for the names ``audit`` receives for float frames.  None: nothing is launched.)
     from .eq import as_eq
 
     eq = as_eq(eq)
@@ -183,6 +186,16 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                 for slot, name in enumerate(("result", "result_no_limiter", "result_no_limiter_normalized")):
                     if returned[slot]:
                         audit(name, dev.audit(outs[slot], n, rate))
+            if visuals is not None:
+                from .visuals import handler_of, make
+
+                draw, sizes = handler_of(visuals)
+                draw("target", make(dev, t_dev, n, rate, sizes))
+                if r_dev is not None:
+                    draw("reference", make(dev, r_dev, nr, rate, sizes))
+                for slot, name in enumerate(("result", "result_no_limiter", "result_no_limiter_normalized")):
+                    if returned[slot]:
+                        draw(name, make(dev, outs[slot], n, rate, sizes))
             if deliveries:
                 from dataclasses import replace
 
