@@ -204,6 +204,72 @@ int mgx_master_shaped(mgx_handle* h, const float* target_dev, int64_t n_target, 
                       float* result_dev, float* result_no_limiter_dev, float* result_no_limiter_normalized_dev,
                       mgx_report* report);
 
+/* Matching EQ tone controls: which part of the spectrum is matched, a side amount of its own, mono bass, and manual trims
+ * (a tilt, up to eight bells and shelves) on top of the match.  Part of the new surface.  They replace step 1 above; steps
+ * 2 and 3 then run on s' unchanged.  With fs = internal_sample_rate, F = fft_size, f_k = (k * fs) / F (the product first:
+ * exact in double), channel c = 0 mid, 1 side, and
+ *     ramp(x)        = 0 for x <= 0,  1 for x >= 1,  0.5 - 0.5 cos(pi x) between
+ *     edge(f, f0, w) = ramp(log2(f / f0) / w + 0.5) for w > 0;   for w == 0: 1 if f >= f0, else 0
+ * per bin k >= 1, float64:
+ *     w  = (low_hz NaN ? 1 : edge(f_k, low_hz, range_octaves)) * (high_hz NaN ? 1 : 1 - edge(f_k, high_hz, range_octaves))
+ *     a  = c == side and side_amount not NaN ? side_amount : shape.amount
+ *     d  = (a * w) * 20 log10(max(s[k], min_value));   d = min(d, max_boost_db);   d = max(d, -max_cut_db)   (NaN cap: none)
+ *     t  = tilt_db_per_octave * log2(f_k / tilt_pivot_hz)
+ *        + sum over the bands whose `channels` name c of
+ *              bell (0):        gain_db / (1 + (q * (f_k / hz - hz / f_k))^2)
+ *              low shelf (1):   gain_db / (1 + (f_k / hz)^(4 q))
+ *              high shelf (2):  gain_db / (1 + (hz / f_k)^(4 q))
+ *     g  = c == side and mono_below_hz not NaN ? edge(f_k, mono_below_hz, mono_octaves) : 1
+ *     s'[k] = 10^((d + t) / 20) * g;     s'[0] = 0
+ * The caps bound the matching part only: the trims are what the caller asked for and are bounded by the field ranges.
+ * Level matching is untouched.  A NEUTRAL tone -- low_hz, high_hz, side_amount and mono_below_hz NaN, tilt 0, no bands --
+ * is the call without a tone, not a multiplication by one.  A NULL shape with a tone is amount 1, no caps, linear phase.
+ * mgx_eq_tone_default: the neutral tone (range_octaves 1, mono_octaves 1, tilt_pivot_hz 1000).
+ * mgx_eq_tone_check: needs no GPU; shape may be NULL.  MGX_ERR_ARGUMENT, the message naming the field: a null cfg or tone;
+ * low_hz outside (0, fs/2), high_hz outside (0, fs/2], low_hz >= high_hz (NaN: open on that side); range_octaves or
+ * mono_octaves outside [0, 4]; side_amount outside [0, 2] (NaN: the shape's amount); mono_below_hz outside (0, fs/2) (NaN:
+ * off); tilt_db_per_octave outside [-6, 6]; tilt_pivot_hz not positive and finite; band_count outside [0, 8]; of a band
+ * below band_count, kind outside {0, 1, 2}, channels outside {1, 2, 3}, hz outside (0, fs/2], gain_db outside [-24, 24],
+ * q outside [0.1, 20] (named bands[i].field); reserved != 0.  Then every refusal of mgx_eq_shape_check(cfg, shape).
+ * mgx_eq_tone_curve: the three per-bin terms of `channel` (0 or 1) on the host, each [F/2 + 1] doubles or NULL: a * w,
+ * t and g; entry 0 of each is 0.  What a front end plots.
+ * mgx_tone_fir: mgx_shape_fir with the tone, for `channel`: float64, host only, a cross-check and NOT what the master
+ * runs.  A NULL or neutral tone is mgx_shape_fir (a NULL shape: the default one).
+ * mgx_master_eq: mgx_master_shaped with a tone (csrc/eq_tone_kernels.h: k_eq_tone runs INSTEAD of k_eq_shape, at the same
+ * point of the design).  A NULL or neutral tone is exactly mgx_master_shaped.  The tone is copied when the call is queued,
+ * as the shape is.  Refusals come before anything is queued.  mgx_last_fir returns the toned taps.  mgx_master_with_fir
+ * is unaffected. */
+#define MGX_EQ_BANDS_MAX 8
+typedef struct mgx_eq_band {
+    int32_t kind;                        /* 0 bell, 1 low shelf, 2 high shelf */
+    int32_t channels;                    /* 1 mid, 2 side, 3 both */
+    double hz;                           /* (0, fs/2] */
+    double gain_db;                      /* [-24, 24] */
+    double q;                            /* [0.1, 20] */
+} mgx_eq_band;
+typedef struct mgx_eq_tone {
+    double low_hz, high_hz;              /* the matching range; NaN: open on that side */
+    double range_octaves;                /* [0, 4]: width of each raised-cosine edge, centred on the edge frequency */
+    double side_amount;                  /* [0, 2], or NaN: the shape's amount */
+    double mono_below_hz;                /* (0, fs/2), or NaN: off */
+    double mono_octaves;                 /* [0, 4] */
+    double tilt_db_per_octave;           /* [-6, 6] */
+    double tilt_pivot_hz;                /* > 0 */
+    int32_t band_count;                  /* [0, MGX_EQ_BANDS_MAX] */
+    int32_t reserved;                    /* 0 */
+    mgx_eq_band bands[MGX_EQ_BANDS_MAX];
+} mgx_eq_tone;
+int mgx_eq_tone_default(mgx_eq_tone* tone);
+int mgx_eq_tone_check(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone);
+int mgx_eq_tone_curve(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone, int32_t channel,
+                      double* weight_times_amount, double* trim_db, double* gate);
+int mgx_tone_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone, int32_t channel,
+                 const double* curve_smooth, double* taps);
+int mgx_master_eq(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
+                  int64_t n_reference, const void* profile_dev, const mgx_config* cfg, const mgx_eq_shape* shape,
+                  const mgx_eq_tone* tone, float* result_dev, float* result_no_limiter_dev,
+                  float* result_no_limiter_normalized_dev, mgx_report* report);
+
 /* match_frequencies.py:104-119 convolve (fftconvolve "same" on mid and side,
  * then ms_to_lr): y = L/R result (n,2), y_mid (n) optional.  taps are host
  * float64 arrays of fft_size entries; `gain` scales both (stages.py:80-88 folded in). */

@@ -20,4 +20,4 @@ from .loudness import Loudness, measure  # noqa: F401  (nor this: BS.1770-4 loud
 from .delivery import Delivered, Delivery, NoiseShaper, TruePeakLimiter  # noqa: F401  (nor this: results at a loudness target, under a true-peak ceiling, dithered)
 from .qc import Audit, AuditLimits, audit  # noqa: F401  (nor this: the quality-control pass over tracks, renderings and written files)
 from .visuals import Overview, Spectrogram, Visuals, VisualsRequest, overview, spectrogram  # noqa: F401  (nor this: waveform overview and spectrogram of frames in HBM)
-from .eq import MatchingEq  # noqa: F401  (nor this: strength, boost / cut caps and minimum phase for the matching EQ)
+from .eq import MatchingEq, ToneBand  # noqa: F401  (nor this: strength, boost / cut caps, minimum phase and tone controls for the matching EQ)

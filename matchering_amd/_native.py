@@ -215,6 +215,39 @@ class MgxEqShape(ctypes.Structure):
     ]
 
 
+EQ_BANDS_MAX = 8                # MGX_EQ_BANDS_MAX
+
+
+class MgxEqBand(ctypes.Structure):
+    """mgx_eq_band (include/mgx.h)."""
+
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("channels", ctypes.c_int32),
+        ("hz", ctypes.c_double),
+        ("gain_db", ctypes.c_double),
+        ("q", ctypes.c_double),
+    ]
+
+
+class MgxEqTone(ctypes.Structure):
+    """mgx_eq_tone (include/mgx.h)."""
+
+    _fields_ = [
+        ("low_hz", ctypes.c_double),
+        ("high_hz", ctypes.c_double),
+        ("range_octaves", ctypes.c_double),
+        ("side_amount", ctypes.c_double),
+        ("mono_below_hz", ctypes.c_double),
+        ("mono_octaves", ctypes.c_double),
+        ("tilt_db_per_octave", ctypes.c_double),
+        ("tilt_pivot_hz", ctypes.c_double),
+        ("band_count", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("bands", MgxEqBand * EQ_BANDS_MAX),
+    ]
+
+
 PROFILE_MAGIC = 0x5250474D      # MGX_PROFILE_MAGIC
 PROFILE_VERSION = 1             # MGX_PROFILE_VERSION
 PROFILE_MERGE_MAX = 64          # MGX_PROFILE_MERGE_MAX
@@ -259,6 +292,15 @@ SYMBOLS = {
     "mgx_shape_fir": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(MgxEqShape), c_double_p, c_double_p]),
     "mgx_master_shaped": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.POINTER(MgxConfig),
                                          ctypes.POINTER(MgxEqShape), _VP, _VP, _VP, ctypes.POINTER(MgxReport)]),
+    "mgx_eq_tone_default": (ctypes.c_int, [ctypes.POINTER(MgxEqTone)]),
+    "mgx_eq_tone_check": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(MgxEqShape), ctypes.POINTER(MgxEqTone)]),
+    "mgx_eq_tone_curve": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(MgxEqShape), ctypes.POINTER(MgxEqTone),
+                                         ctypes.c_int32, c_double_p, c_double_p, c_double_p]),
+    "mgx_tone_fir": (ctypes.c_int, [ctypes.POINTER(MgxConfig), ctypes.POINTER(MgxEqShape), ctypes.POINTER(MgxEqTone),
+                                    ctypes.c_int32, c_double_p, c_double_p]),
+    "mgx_master_eq": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.POINTER(MgxConfig),
+                                     ctypes.POINTER(MgxEqShape), ctypes.POINTER(MgxEqTone), _VP, _VP, _VP,
+                                     ctypes.POINTER(MgxReport)]),
     "mgx_convolve": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int32,
                                     ctypes.c_double, _VP, _VP, c_double_p]),
     "mgx_host_alloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_VP)]),

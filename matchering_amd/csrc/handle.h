@@ -196,6 +196,8 @@ struct mgx_handle {
         float* out[3] = {nullptr, nullptr, nullptr};
         bool shaped = false;                // mgx_master_shaped with a shape: `shape` is the call's own copy
         mgx_eq_shape shape = {};
+        bool toned = false;                 // mgx_master_eq with a tone that is not neutral: `tone` likewise (then `shaped`)
+        mgx_eq_tone tone = {};
     } last_call;
     bool avoid_tail = false;                // sticky after such a report: rounds 1..K-1 as one launch each (MGX_NO_TAIL=1: always)
     bool requeued = false;                  // the last check_device_error queued the call again

@@ -56,7 +56,8 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const Ma
     // the level gain of stages.py:80-88 (a device scalar) folded into the filter spectra
     {
         StageScope scope(h, MGX_STAGE_DESIGN_FIR);
-        MGX_TRY(run_fir_design(h, &c.cfg, tw, rw, c.fir_given, c.profile, c.shaped ? &c.shape : nullptr));
+        MGX_TRY(run_fir_design(h, &c.cfg, tw, rw, c.fir_given, c.profile, c.shaped ? &c.shape : nullptr,
+                               c.toned ? &c.tone : nullptr));
     }
     MGX_TRY(ensure(h, h->y, (size_t)c.n_target * sizeof(float2)));
     MGX_TRY(ensure(h, h->mid, (size_t)c.n_target * sizeof(float)));
@@ -103,10 +104,15 @@ static int queue_master(mgx_handle* h, const mgx_handle::MasterCall& c, const Ma
 static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
                        int64_t n_reference, const mgx_profile_header* profile, const mgx_config* cfg,
                        const float* fir_given, float* result_dev, float* result_no_limiter_dev,
-                       float* result_no_limiter_normalized_dev, mgx_report* report, const mgx_eq_shape* shape = nullptr) {
+                       float* result_no_limiter_normalized_dev, mgx_report* report, const mgx_eq_shape* shape = nullptr,
+                       const mgx_eq_tone* tone = nullptr) {
     if (!h || !target_dev || (!reference_dev && !profile)) return fail(MGX_ERR_ARGUMENT, "null argument");
     MGX_TRY(check_config(cfg));
-    if (shape) MGX_TRY(mgx_eq_shape_check(cfg, shape));       // (refused by name before anything is queued)
+    if (tone) MGX_TRY(mgx_eq_tone_check(cfg, shape, tone));   // (refused by name before anything is queued)
+    else if (shape) MGX_TRY(mgx_eq_shape_check(cfg, shape));
+    if (eq_tone_neutral(tone)) tone = nullptr;                  // the call without a tone: today's route
+    const mgx_eq_shape tone_alone{1.0, std::nan(""), std::nan(""), 0, 0};
+    if (tone && !shape) shape = &tone_alone;                    // (a NULL shape with a tone: amount 1, no caps, linear phase)
     HIP_TRY(hipSetDevice(h->device));
     LimiterParams lp{};
     if (result_dev) {               // derived (and validated) once, before any work is queued
@@ -125,6 +131,8 @@ static int master_impl(mgx_handle* h, const float* target_dev, int64_t n_target,
     call.cfg = *cfg;
     call.shaped = shape != nullptr;
     if (shape) call.shape = *shape;                             // (the call's own copy: the caller's may change behind it)
+    call.toned = tone != nullptr;
+    if (tone) call.tone = *tone;
     call.out[0] = result_dev;
     call.out[1] = result_no_limiter_dev;
     call.out[2] = result_no_limiter_normalized_dev;

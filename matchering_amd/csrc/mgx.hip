@@ -32,6 +32,7 @@
 #include "deliver_shaped_kernel.h"
 #include "audit_kernel.h"
 #include "visuals_kernel.h"
+#include "eq_tone_kernels.h"           // (last: only a call with a tone launches it, and it moves no other kernel)
 
 #include "mgx_policy.h"
 #include "handle.h"
@@ -818,6 +819,18 @@ int mgx_master_shaped(mgx_handle* h, const float* target_dev, int64_t n_target, 
     return master_impl(h, target_dev, n_target, reference_dev, profile_dev ? 0 : n_reference,
                        (const mgx_profile_header*)profile_dev, cfg, nullptr, result_dev, result_no_limiter_dev,
                        result_no_limiter_normalized_dev, report, shape);
+}
+
+// ... and its tone controls (mgx_eq_tone_check, mgx_eq_tone_curve, mgx_tone_fir: mgx_policy.cpp)
+int mgx_master_eq(mgx_handle* h, const float* target_dev, int64_t n_target, const float* reference_dev,
+                  int64_t n_reference, const void* profile_dev, const mgx_config* cfg, const mgx_eq_shape* shape,
+                  const mgx_eq_tone* tone, float* result_dev, float* result_no_limiter_dev,
+                  float* result_no_limiter_normalized_dev, mgx_report* report) {
+    if ((reference_dev != nullptr) == (profile_dev != nullptr))
+        return fail(MGX_ERR_ARGUMENT, "mgx_master_eq takes a reference track or a reference profile, exactly one of them");
+    return master_impl(h, target_dev, n_target, reference_dev, profile_dev ? 0 : n_reference,
+                       (const mgx_profile_header*)profile_dev, cfg, nullptr, result_dev, result_no_limiter_dev,
+                       result_no_limiter_normalized_dev, report, shape, tone);
 }
 
 // ---- reference profiles (mgx_profile_bytes: mgx_policy.cpp) --------------------

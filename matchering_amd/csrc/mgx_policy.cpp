@@ -9,6 +9,7 @@
 #include <memory>
 #include <vector>
 
+#include "eq_tone.h"
 #include "fir_plan.h"
 #include "host_params.h"
 
@@ -326,6 +327,10 @@ bool eq_shape_curve_stage(const mgx_eq_shape* shape) {
     return shape && (shape->amount != 1.0 || !std::isnan(shape->max_boost_db) || !std::isnan(shape->max_cut_db));
 }
 bool eq_shape_minimum_phase(const mgx_eq_shape* shape) { return shape && shape->phase == 1; }
+bool eq_tone_neutral(const mgx_eq_tone* tone) {
+    return !tone || (std::isnan(tone->low_hz) && std::isnan(tone->high_hz) && std::isnan(tone->side_amount) &&
+                     std::isnan(tone->mono_below_hz) && tone->tilt_db_per_octave == 0.0 && tone->band_count == 0);
+}
 
 // in-place radix-2 complex transform of n = 2^k points for mgx_shape_fir: sign -1 forward, +1 inverse, unnormalised.
 // Every twiddle is its own cos / sin of an exactly representable fraction of the circle.
@@ -420,25 +425,9 @@ int mgx_eq_shape_check(const mgx_config* cfg, const mgx_eq_shape* shape) {
     return 0;
 }
 
-int mgx_shape_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const double* curve_smooth, double* taps) {
-    if (!cfg || !shape || !curve_smooth || !taps) return fail(MGX_ERR_ARGUMENT, "null argument");
-    const char* const refusal = "bad fft_size";                 // (no upper bound, as for mgx_design_fir)
-    MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
-    MGX_TRY(eq_shape_values(shape));                            // (the upper end of the size range is the device's)
+// steps 2 and 3 of the definition on a shaped curve s[0 .. F/2] (fft_size and the shape's values are the caller's to check)
+static int fir_from_shaped_curve(const mgx_config* cfg, const mgx_eq_shape* shape, const std::vector<double>& s, double* taps) {
     const int f = cfg->fft_size, half = f / 2;
-    if (shape->phase == 1 && f < EQ_MINPHASE_FFT_MIN)
-        return fail(MGX_ERR_UNSUPPORTED, "a minimum-phase matching EQ needs fft_size 64 or more, not " + std::to_string(f));
-    // 1. shape
-    std::vector<double> s(curve_smooth, curve_smooth + half + 1);
-    if (eq_shape_curve_stage(shape)) {
-        s[0] = 0.0;
-        for (int k = 1; k <= half; ++k) {
-            double d = shape->amount * (20.0 * std::log10(std::max(s[k], cfg->min_value)));
-            if (!std::isnan(shape->max_boost_db)) d = std::min(d, shape->max_boost_db);
-            if (!std::isnan(shape->max_cut_db)) d = std::max(d, -shape->max_cut_db);
-            s[k] = std::pow(10.0, d / 20.0);
-        }
-    }
     // 2. linear-phase taps: the design's own synthesis
     {
         const std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(fir_design_params(*cfg));
@@ -469,6 +458,129 @@ int mgx_shape_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const double
         taps[half + j] = x[j].real() / n * taper;
     }
     return 0;
+}
+
+int mgx_shape_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const double* curve_smooth, double* taps) {
+    if (!cfg || !shape || !curve_smooth || !taps) return fail(MGX_ERR_ARGUMENT, "null argument");
+    const char* const refusal = "bad fft_size";                 // (no upper bound, as for mgx_design_fir)
+    MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
+    MGX_TRY(eq_shape_values(shape));                            // (the upper end of the size range is the device's)
+    const int f = cfg->fft_size, half = f / 2;
+    if (shape->phase == 1 && f < EQ_MINPHASE_FFT_MIN)
+        return fail(MGX_ERR_UNSUPPORTED, "a minimum-phase matching EQ needs fft_size 64 or more, not " + std::to_string(f));
+    // 1. shape
+    std::vector<double> s(curve_smooth, curve_smooth + half + 1);
+    if (eq_shape_curve_stage(shape)) {
+        s[0] = 0.0;
+        for (int k = 1; k <= half; ++k) {
+            double d = shape->amount * (20.0 * std::log10(std::max(s[k], cfg->min_value)));
+            if (!std::isnan(shape->max_boost_db)) d = std::min(d, shape->max_boost_db);
+            if (!std::isnan(shape->max_cut_db)) d = std::max(d, -shape->max_cut_db);
+            s[k] = std::pow(10.0, d / 20.0);
+        }
+    }
+    return fir_from_shaped_curve(cfg, shape, s, taps);
+}
+
+// ---- matching EQ tone controls ----------------------------------------------------
+static const mgx_eq_shape EQ_SHAPE_DEFAULT = {1.0, std::nan(""), std::nan(""), 0, 0};      // a NULL shape with a tone
+
+int mgx_eq_tone_default(mgx_eq_tone* tone) {
+    if (!tone) return fail(MGX_ERR_ARGUMENT, "tone: null");
+    std::memset(tone, 0, sizeof(*tone));
+    tone->low_hz = tone->high_hz = tone->side_amount = tone->mono_below_hz = std::nan("");
+    tone->range_octaves = tone->mono_octaves = 1.0;
+    tone->tilt_pivot_hz = 1000.0;
+    return 0;
+}
+
+// the values of a tone at a sample rate
+static int eq_tone_values(const mgx_config* cfg, const mgx_eq_tone* tone) {
+    if (cfg->internal_sample_rate <= 0) return fail(MGX_ERR_ARGUMENT, "internal_sample_rate must be positive");
+    const double nyquist = 0.5 * cfg->internal_sample_rate;
+    const std::string top = " at " + std::to_string(cfg->internal_sample_rate) + " Hz";
+    auto inside = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
+    if (!std::isnan(tone->low_hz) && !(std::isfinite(tone->low_hz) && tone->low_hz > 0.0 && tone->low_hz < nyquist))
+        return fail(MGX_ERR_ARGUMENT, "low_hz: outside (0, fs/2)" + top + " (NaN: open)");
+    if (!std::isnan(tone->high_hz) && !(std::isfinite(tone->high_hz) && tone->high_hz > 0.0 && tone->high_hz <= nyquist))
+        return fail(MGX_ERR_ARGUMENT, "high_hz: outside (0, fs/2]" + top + " (NaN: open)");
+    if (!std::isnan(tone->low_hz) && !std::isnan(tone->high_hz) && !(tone->low_hz < tone->high_hz))
+        return fail(MGX_ERR_ARGUMENT, "low_hz: must lie below high_hz");
+    if (!inside(tone->range_octaves, 0.0, 4.0)) return fail(MGX_ERR_ARGUMENT, "range_octaves: outside [0, 4]");
+    if (!std::isnan(tone->side_amount) && !inside(tone->side_amount, 0.0, 2.0))
+        return fail(MGX_ERR_ARGUMENT, "side_amount: outside [0, 2] (NaN: the shape's amount)");
+    if (!std::isnan(tone->mono_below_hz) &&
+        !(std::isfinite(tone->mono_below_hz) && tone->mono_below_hz > 0.0 && tone->mono_below_hz < nyquist))
+        return fail(MGX_ERR_ARGUMENT, "mono_below_hz: outside (0, fs/2)" + top + " (NaN: off)");
+    if (!inside(tone->mono_octaves, 0.0, 4.0)) return fail(MGX_ERR_ARGUMENT, "mono_octaves: outside [0, 4]");
+    if (!inside(tone->tilt_db_per_octave, -6.0, 6.0)) return fail(MGX_ERR_ARGUMENT, "tilt_db_per_octave: outside [-6, 6]");
+    if (!(std::isfinite(tone->tilt_pivot_hz) && tone->tilt_pivot_hz > 0.0))
+        return fail(MGX_ERR_ARGUMENT, "tilt_pivot_hz: must be positive and finite");
+    if (tone->band_count < 0 || tone->band_count > MGX_EQ_BANDS_MAX)
+        return fail(MGX_ERR_ARGUMENT, "band_count: outside [0, " + std::to_string(MGX_EQ_BANDS_MAX) + "]");
+    for (int i = 0; i < tone->band_count; ++i) {
+        const mgx_eq_band& b = tone->bands[i];
+        const std::string name = "bands[" + std::to_string(i) + "].";
+        if (b.kind < 0 || b.kind > 2) return fail(MGX_ERR_ARGUMENT, name + "kind: 0 (bell), 1 (low shelf) or 2 (high shelf)");
+        if (b.channels < 1 || b.channels > 3) return fail(MGX_ERR_ARGUMENT, name + "channels: 1 (mid), 2 (side) or 3 (both)");
+        if (!(std::isfinite(b.hz) && b.hz > 0.0 && b.hz <= nyquist)) return fail(MGX_ERR_ARGUMENT, name + "hz: outside (0, fs/2]" + top);
+        if (!inside(b.gain_db, -24.0, 24.0)) return fail(MGX_ERR_ARGUMENT, name + "gain_db: outside [-24, 24]");
+        if (!inside(b.q, 0.1, 20.0)) return fail(MGX_ERR_ARGUMENT, name + "q: outside [0.1, 20]");
+    }
+    if (tone->reserved != 0) return fail(MGX_ERR_ARGUMENT, "reserved: must be 0");
+    return 0;
+}
+
+int mgx_eq_tone_check(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone) {
+    if (!cfg || !tone) return fail(MGX_ERR_ARGUMENT, "null argument");
+    MGX_TRY(eq_tone_values(cfg, tone));
+    return shape ? mgx_eq_shape_check(cfg, shape) : 0;
+}
+
+static EqToneArgs eq_tone_args(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone) {
+    return EqToneArgs{shape->amount, shape->max_boost_db, shape->max_cut_db, cfg->min_value, *tone,
+                      (double)cfg->internal_sample_rate, cfg->fft_size};
+}
+
+int mgx_eq_tone_curve(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone, int32_t channel,
+                      double* weight_times_amount, double* trim_db, double* gate) {
+    if (!cfg || !tone) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (channel != 0 && channel != 1) return fail(MGX_ERR_ARGUMENT, "channel: 0 (mid) or 1 (side)");
+    const char* const refusal = "bad fft_size";
+    MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
+    if (!shape) shape = &EQ_SHAPE_DEFAULT;
+    MGX_TRY(eq_tone_values(cfg, tone));
+    MGX_TRY(eq_shape_values(shape));
+    const EqToneArgs a = eq_tone_args(cfg, shape, tone);
+    for (int k = 0; k <= cfg->fft_size / 2; ++k) {
+        const EqToneTerms t = k == 0 ? EqToneTerms{0.0, 0.0, 0.0} : eq_tone_terms(k, channel, a);
+        if (weight_times_amount) weight_times_amount[k] = t.weight_times_amount;
+        if (trim_db) trim_db[k] = t.trim_db;
+        if (gate) gate[k] = t.gate;
+    }
+    return 0;
+}
+
+int mgx_tone_fir(const mgx_config* cfg, const mgx_eq_shape* shape, const mgx_eq_tone* tone, int32_t channel,
+                 const double* curve_smooth, double* taps) {
+    if (!cfg || !curve_smooth || !taps) return fail(MGX_ERR_ARGUMENT, "null argument");
+    if (channel != 0 && channel != 1) return fail(MGX_ERR_ARGUMENT, "channel: 0 (mid) or 1 (side)");
+    if (!shape) shape = &EQ_SHAPE_DEFAULT;
+    if (tone) {
+        const char* const refusal = "bad fft_size";
+        MGX_TRY(check_fft_size(cfg->fft_size, INT_MAX, refusal, refusal, MGX_ERR_ARGUMENT, refusal));
+        MGX_TRY(eq_tone_values(cfg, tone));
+    }
+    if (eq_tone_neutral(tone)) return mgx_shape_fir(cfg, shape, curve_smooth, taps);      // the route without a tone
+    MGX_TRY(eq_shape_values(shape));
+    const int f = cfg->fft_size, half = f / 2;
+    if (shape->phase == 1 && f < EQ_MINPHASE_FFT_MIN)
+        return fail(MGX_ERR_UNSUPPORTED, "a minimum-phase matching EQ needs fft_size 64 or more, not " + std::to_string(f));
+    // 1. the tone stage in place of the shape stage
+    std::vector<double> s(curve_smooth, curve_smooth + half + 1);
+    const EqToneArgs a = eq_tone_args(cfg, shape, tone);
+    for (int k = 0; k <= half; ++k) eq_tone_phase(k, channel, s.data(), a);
+    return fir_from_shaped_curve(cfg, shape, s, taps);
 }
 
 int mgx_loudness_gate(const double* sub_energy, int64_t count, int32_t sample_rate, mgx_loudness_report* report) {

@@ -1,7 +1,8 @@
 // The part of libmgx.so that touches no device (mgx_policy.cpp): the calling thread's error text, the validation of a
 // Config, the entry points that are arithmetic on the structs of include/mgx.h -- mgx_version, mgx_last_error,
 // mgx_config_default, mgx_design_fir, mgx_loudness_gate, mgx_audit_gate, mgx_spectrogram_plan, mgx_delivery_gain, mgx_delivery_limit_step, their _shaped forms,
-// mgx_noise_shaper_preset, mgx_profile_bytes, mgx_eq_shape_check, mgx_shape_fir --
+// mgx_noise_shaper_preset, mgx_profile_bytes, mgx_eq_shape_check, mgx_shape_fir, mgx_eq_tone_default, mgx_eq_tone_check,
+// mgx_eq_tone_curve, mgx_tone_fir --
 // and what the device entry points settle from their numbers alone before they touch a handle.
 // No HIP here: g++ compiles the unit by itself (tests/emu/emu_policy_driver.cpp runs it under the sanitizers), and
 // mgx.hip uses what is declared below.
@@ -76,5 +77,8 @@ int profile_merge_check(const void* const* profiles_dev, const int32_t* weights,
 constexpr int EQ_MINPHASE_FFT_MIN = 64, EQ_MINPHASE_FFT_MAX = 16384;
 bool eq_shape_curve_stage(const mgx_eq_shape* shape);          // amount != 1 or a cap: k_eq_shape runs
 bool eq_shape_minimum_phase(const mgx_eq_shape* shape);
+// its tone controls (mgx_eq_tone): true for NULL and for a tone that asks for nothing -- the call then takes the route
+// without a tone (k_eq_shape or no launch), not k_eq_tone with factors of one
+bool eq_tone_neutral(const mgx_eq_tone* tone);
 
 }  // namespace mgx

@@ -214,9 +214,10 @@ static int run_minimum_phase(mgx_handle* h, CallContext& cx, int fft) {
 // fir_given: a FIR pair to use instead of the designed one (album mode), or null.  profile: the reference as a profile
 // (then `rw` is not looked at), or null
 // shape: the matching EQ's controls (include/mgx.h, mgx_eq_shape; checked by the caller), or null
+// tone: its tone controls (mgx_eq_tone; checked by the caller, not neutral, and then `shape` is not null), or null
 static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork& tw, const TrackWork& rw,
                           const float* fir_given, const mgx_profile_header* profile = nullptr,
-                          const mgx_eq_shape* shape = nullptr) {
+                          const mgx_eq_shape* shape = nullptr, const mgx_eq_tone* tone = nullptr) {
     CallContext& cx = context(h);
     std::shared_ptr<FirPlanHost> plan = FirPlanHost::get(fir_design_params(*cfg));
     // no operator when LOWESS is not linear (robustness passes): the chain runs on the curve itself.  Otherwise the
@@ -295,8 +296,13 @@ static int run_fir_design(mgx_handle* h, const mgx_config* cfg, const TrackWork&
         hipLaunchKernelGGL(k_fir_matvec, dim3(pl.bins), dim3(256), 0, h->fq, pl, (const double*)pd.M,
                            (const int2*)pd.band, (const double*)raw, scratch);
     }
-    // the matching EQ's shape stage, in place on the two smooth planes: launched only where it changes the curve
-    if (eq_shape_curve_stage(shape))
+    // the matching EQ's shape stage, in place on the two smooth planes: launched only where it changes the curve.  With
+    // a tone the tone stage runs in its place (eq_tone_kernels.h): one launch either way
+    if (tone && shape)
+        hipLaunchKernelGGL(k_eq_tone, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->fq, pl, scratch,
+                           EqToneArgs{shape->amount, shape->max_boost_db, shape->max_cut_db, cfg->min_value, *tone,
+                                      (double)cfg->internal_sample_rate, cfg->fft_size});
+    else if (eq_shape_curve_stage(shape))
         hipLaunchKernelGGL(k_eq_shape, dim3((pl.bins + 255) / 256, 2), dim3(256), 0, h->fq, pl, scratch,
                            EqShapeArgs{shape->amount, shape->max_boost_db, shape->max_cut_db, cfg->min_value});
     if (pl.fft < 64) {                                          // 8 .. 32 taps: the plain cosine sum, one thread per tap

@@ -658,7 +658,8 @@ class Device:
         holding [2][fft_size] float32) replaces the designed matching FIR: ``mgx_master_with_fir``.  ``profile``
         (a DeviceBuffer holding a reference profile) stands for the reference, which is then None:
         ``mgx_master_with_profile``.  ``eq`` (an ``eq.MatchingEq``) shapes the FIR that is designed:
-        ``mgx_master_shaped``, on either route; a given ``fir`` is used as given, whatever ``eq`` says."""
+        ``mgx_master_shaped``, on either route -- ``mgx_master_eq`` where it carries tone controls that are not neutral; a
+        given ``fir`` is used as given, whatever ``eq`` says."""
         report = MgxReport() if want_report else None
 
         def p(b):
@@ -667,7 +668,13 @@ class Device:
         rep = ctypes.byref(report) if report is not None else None
         if profile is not None and reference is not None:
             raise ValueError("master: a reference track or a reference profile, not both")
-        if eq is not None and fir is None:
+        tone = eq.tone_native() if eq is not None and fir is None else None
+        if tone is not None:                                # (not neutral: k_eq_tone in place of k_eq_shape)
+            check(library().mgx_master_eq(
+                self.handle, p(target), n_target, p(reference), n_reference, p(profile), ctypes.byref(native_config),
+                ctypes.byref(eq.to_native()), ctypes.byref(tone), p(result), p(result_no_limiter),
+                p(result_no_limiter_normalized), rep))
+        elif eq is not None and fir is None:
             check(library().mgx_master_shaped(
                 self.handle, p(target), n_target, p(reference), n_reference, p(profile), ctypes.byref(native_config),
                 ctypes.byref(eq.to_native()), p(result), p(result_no_limiter), p(result_no_limiter_normalized), rep))
