@@ -210,6 +210,10 @@ struct ConvWide {
 
     // ---- last inverse pass + epilogue: real = mid, imaginary = side; L = mid + side, R = mid - side (dsp.py:67-68).
     // Returns the thread's max(|L|,|R|) over frames of the track; stores past its end are dropped by the range check.
+    // END_BRANCH: only the track's last block can reach past its end, so every other block takes the plain maximum and
+    // the frame-count compare runs behind a uniform branch, over the pass's outputs once more (k_conv_wide's form;
+    // without it every frame of every block is compared, the form the CPU emulation keeps as its reference).
+    template <bool END_BRANCH = false>
     static MGX_HD float phase_store(int tid, long long b, const Conv2Args& a, const Persist& ps, const float2* lds) {
         float peak = 0.f;
         typename F::Tw0Full tw;
@@ -217,12 +221,14 @@ struct ConvWide {
         const MemView dst = mem_view(a.y, a.n * 8);
         const MemView dm = mem_view(a.ymid, a.ymid ? a.n * 4 : 0);
         const unsigned frames = (unsigned)a.n, o0 = (unsigned)first_output(b);
+        const bool to_the_end = first_output(b) + HOP > a.n;       // (uniform)
         MGX_UNROLL
         for (int c = 0; c < CNT0; ++c) {
             const unsigned first = o0 + (unsigned)(tid + c * T);
             float2 v[R0];
             if constexpr (CNT0 == 1) F::inv0_load_lean(v, tid, ps.tw0, lds);
             else F::inv0_load(v, tid, c, tw, lds);
+            float inside = 0.f;
             MGX_UNROLL
             for (int j = 0; j < KEEP; ++j) {
                 const float2 ms = v[SKIP + j];
@@ -230,8 +236,19 @@ struct ConvWide {
                 st_f2<CONV_STORE_AUX>(dst, first * 8u, (unsigned)(j * S0 * 8), y);
                 st_f1<CONV_STORE_AUX>(dm, first * 4u, (unsigned)(j * S0 * 4), ms.x);
                 const float p = fmaxf(fabsf(y.x), fabsf(y.y));
-                peak = fmaxf(peak, first + (unsigned)(j * S0) < frames ? p : 0.f);
+                if (END_BRANCH) inside = fmaxf(inside, p);
+                else inside = fmaxf(inside, first + (unsigned)(j * S0) < frames ? p : 0.f);
             }
+            if (END_BRANCH && to_the_end) {
+                inside = 0.f;
+                MGX_UNROLL
+                for (int j = 0; j < KEEP; ++j) {
+                    const float2 ms = v[SKIP + j];
+                    const float p = fmaxf(fabsf(ms.x + ms.y), fabsf(ms.x - ms.y));
+                    inside = fmaxf(inside, first + (unsigned)(j * S0) < frames ? p : 0.f);
+                }
+            }
+            peak = fmaxf(peak, inside);
         }
         return peak;
     }

@@ -268,12 +268,27 @@ __device__ __forceinline__ long long conv_wide_block(unsigned w, unsigned round,
     if ((grid & 7u) == 0) return ((long long)round * 8 + (w & 7u)) * (grid >> 3) + (w >> 3);
     return (long long)round * grid + w;
 }
+// Which forms of the loop the kernel runs (conv_wide_kernel.h; the earlier form of each stays there as the CPU emulation's
+// reference, and an A/B build clears a bit in a copy of this line): the block peak combined behind the NEXT block's
+// first barrier, the end-of-track mask behind a last-block branch.  (Two more lost their A/B and are gone, DESIGN.md
+// section 3.4: 16-byte global accesses with an exchange between neighbouring lanes, filter tables that hold P and Q.)
+constexpr unsigned CONV_WIDE_LATE_PEAK = 2, CONV_WIDE_END_BRANCH = 8;
+constexpr unsigned CONV_WIDE_FORMS = CONV_WIDE_LATE_PEAK | CONV_WIDE_END_BRANCH;
+// the block peak from the waves' maxima (thread 0; behind a barrier that follows the waves' writes)
+template <int THREADS>
+__device__ __forceinline__ float combine_wave_peaks(const float* scratch) {
+    float r = 0.f;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; ++w) r = fmaxf(r, scratch[w]);
+    return r;
+}
 template <int LOG2N>
 __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) void k_conv_wide(Conv2Args a) {
     warm_code(CODE_CONV, CODE_VARIANT_CONV_WIDE);
     using CW = ConvWide<LOG2N>;
     using CB = Conv2Block<LOG2N>;
     using F = Fft2<LOG2N>;
+    constexpr bool LATE_PEAK = (CONV_WIDE_FORMS & CONV_WIDE_LATE_PEAK) != 0, END_BRANCH = (CONV_WIDE_FORMS & CONV_WIDE_END_BRANCH) != 0;
     MGX_LDS;
     float2* lds = reinterpret_cast<float2*>(mgx_smem);
     float2* mid_table = lds + F::LDS_ELEMS;
@@ -284,6 +299,7 @@ __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) v
     typename CW::Frames frames;
     CW::fetch(tid, conv_wide_block(blockIdx.x, 0, gridDim.x), a, frames);
     __syncthreads();
+    long long pending = -1;                               // LATE_PEAK: the block whose waves' maxima wait in `scratch`
     for (unsigned round = 0;; ++round) {
         const long long b = conv_wide_block(blockIdx.x, round, gridDim.x);
         if (b >= a.npairs) break;
@@ -296,6 +312,7 @@ __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) v
 #endif
         CW::phase_pass0(opaque(tid), ps, frames, lds);
         lds_barrier();
+        if (LATE_PEAK && tid == 0 && pending >= 0 && a.pair_peak) a.pair_peak[pending] = combine_wave_peaks<F::T>(scratch);
         DEV_CONV_MARK(0);                   // pass 0, barrier
         fwd_middle_passes<F>(opaque(tid), lds, mid_table);
         __builtin_amdgcn_sched_barrier(0);
@@ -317,10 +334,27 @@ __global__ __launch_bounds__((Fft2<LOG2N>::T), (conv_waves_per_simd<LOG2N>())) v
         CW::fetch(opaque(tid), conv_wide_block(blockIdx.x, round + 1, gridDim.x), a, frames);
         lds_barrier();
         DEV_CONV_MARK(4);                   // row back, inverse middle passes, barrier
-        const float pk = CW::phase_store(opaque(tid), b, a, ps, lds);
-        const float bp = block_max_lds<F::T>(pk, scratch);      // (a barrier inside: the LDS is free for the next block)
-        if (tid == 0 && a.pair_peak) a.pair_peak[b] = bp;
+        const float pk = CW::template phase_store<END_BRANCH>(opaque(tid), b, a, ps, lds);
+        if constexpr (LATE_PEAK) {
+            // No barrier between this phase and the next block's pass 0.  None is needed for the transform: the
+            // inverse pass 0 above read LDS positions base<0>(tid) + off<0>(q), and the forward pass 0 of the next
+            // block writes exactly those -- the thread's own (one pass-0 butterfly per thread).  The barrier that
+            // stood here served the peak alone and kept sixteen waves in lock step across two phases that mix memory,
+            // VALU and LDS work.  The waves' maxima wait in `scratch`; thread 0 combines them behind the barrier that
+            // follows the next pass 0 (or the loop), and the waves write the next block's only behind three more.
+            static_assert(F::CNT(0) == 1, "a thread's inverse pass 0 reads what its own forward pass 0 writes, nothing else");
+            const float wave_peak = wave_max(pk);
+            if ((tid & 63) == 0) scratch[tid >> 6] = wave_peak;
+            pending = b;
+        } else {
+            const float bp = block_max_lds<F::T>(pk, scratch);      // (a barrier inside: the LDS is free for the next block)
+            if (tid == 0 && a.pair_peak) a.pair_peak[b] = bp;
+        }
         DEV_CONV_MARK(5);                   // inverse pass 0, stores, peak
+    }
+    if (LATE_PEAK && pending >= 0) {                      // (uniform) the last block's peak
+        lds_barrier();
+        if (tid == 0 && a.pair_peak) a.pair_peak[pending] = combine_wave_peaks<F::T>(scratch);
     }
 }
 // its filter spectra: grid = 2 (mid, side); taps = [2][N/4] float
