@@ -681,6 +681,59 @@ int mgx_audit(mgx_handle* h, const void* x_dev, int64_t n_frames, int32_t bits, 
               int64_t* count);
 int mgx_audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int32_t sample_rate, mgx_audit_report* report);
 
+/* Clip repair: the short flat tops of a track that was clipped, rebuilt from the samples around them while the frames
+ * are in HBM (the reference warns about a clipping target, checker.py, and masters it as it is).  Opt-in, part of the
+ * new surface, like the audit that counts such runs.  DESIGN.md section 3.20.  Each channel on its own:
+ *   input: x[n][2] float32; level L > 0, min_run >= 1, min_run <= max_run <= MGX_DECLIP_MAX_RUN, max_rise K >= 1.
+ *   per sample, xd = (double)x[i]: high = finite and xd >= L; low = finite and xd <= -L.
+ *   run [a, b): a maximal sequence of consecutive high samples, or of consecutive low ones; r = b - a.  A NaN or an
+ *     infinity ends a run; a low run may follow a high one at once.
+ *   a run is REPAIRED iff min_run <= r <= max_run, a >= 2, b + 1 <= n - 1 and the four anchors x[a-2], x[a-1], x[b],
+ *     x[b+1] are finite.  Every other run is left as it is and counted once: short (r < min_run), else long
+ *     (r > max_run), else edge (it lacks four finite anchors).
+ *   a repaired run, from the anchors' ORIGINAL values (runs are independent of each other), every operation float64
+ *   and rounded on its own (no fused multiply-add):
+ *     h = (double)(r + 1);  p0 = x[a-1];  p1 = x[b];  m0 = h * (p0 - x[a-2]);  m1 = h * (x[b+1] - p1)
+ *     for i = a - 1 + k, k = 1..r:   t = k / h;  t2 = t * t;  t3 = t2 * t
+ *       y = ((2*t3 - 3*t2 + 1) * p0 + (t3 - 2*t2 + t) * m0) + ((3*t2 - 2*t3) * p1 + (t3 - t2) * m1)
+ *     (sums from left to right): the cubic Hermite segment through the two inner anchors with the one-sided slopes.
+ *     high run:  if (y > K L) y = K L;    out[i] = y > xd ? (float)y : x[i]         (K L is one product)
+ *     low run:   if (y < -K L) y = -K L;  out[i] = y < xd ? (float)y : x[i]
+ *   every other sample is copied bit for bit, the ones that are not finite included.
+ *   report, per channel c: runs_repaired[c]; samples_repaired[c], the samples inside those runs; samples_raised[c], the
+ *     samples whose output bits differ from the input's; longest_repaired[c] (0: none); first_repaired[c], the first
+ *     frame of the first repaired run (-1: none); runs_short[c], runs_long[c], runs_edge[c]; peak_before[c] and
+ *     peak_after[c] = max |.| over the finite samples of the input and of the output.
+ * mgx_declip_check needs no GPU.  MGX_ERR_ARGUMENT, the message naming the field: params null; level not finite or
+ * <= 0; max_rise not finite or < 1; min_run < 1; max_run outside [min_run, MGX_DECLIP_MAX_RUN].
+ * mgx_declip: n_frames frames of x_dev -> out_dev in two launches on the handle's stream (csrc/declip_kernel.h: k_declip,
+ * a workgroup per 4096 frames with a halo of max-run + 2 frames either side; k_declip_fold, which folds the workgroups'
+ * counters), none of whose workgroups waits for another; no atomics: two calls on the same input give the same bytes.
+ * Queued; it waits for the result only where `report` (host, may be NULL) is given.  n_frames == 0 succeeds, launches
+ * nothing and reports zeros and -1.  MGX_ERR_ARGUMENT beyond mgx_declip_check's: a null h, x_dev or out_dev; n_frames
+ * negative; x_dev or out_dev not 16-byte aligned (what mgx_malloc returns is); out_dev overlapping x_dev (out of place
+ * only: a workgroup reads its neighbours' frames).  MGX_ERR_UNSUPPORTED: more than 500 million frames.  The handle is
+ * good for the next call.
+ * mgx_declip_report_read: the report of the handle's most recent mgx_declip call, for a caller that queued it without
+ * one and reads it where it waits anyway; it waits for the stream.  Zeros and -1 where that call had no frames or there
+ * was none.  MGX_ERR_ARGUMENT: a null h or report. */
+#define MGX_DECLIP_MAX_RUN 512
+typedef struct mgx_declip_params {
+    double level;                        /* linear */
+    double max_rise;                     /* a repaired sample stays within max_rise * level */
+    int32_t min_run;                     /* samples */
+    int32_t max_run;
+} mgx_declip_params;
+typedef struct mgx_declip_report {
+    int64_t runs_repaired[2], samples_repaired[2], samples_raised[2], longest_repaired[2], first_repaired[2];
+    int64_t runs_short[2], runs_long[2], runs_edge[2];
+    double peak_before[2], peak_after[2];
+} mgx_declip_report;
+int mgx_declip_check(const mgx_declip_params* params);
+int mgx_declip(mgx_handle* h, const float* x_dev, int64_t n_frames, const mgx_declip_params* params, float* out_dev,
+               mgx_declip_report* report);
+int mgx_declip_report_read(mgx_handle* h, mgx_declip_report* report);
+
 /* Visuals: the pictures a mastering front end shows -- a waveform overview and a spectrogram -- computed from (n, 2)
  * float32 frames while they are in HBM; what comes back is a few hundred kilobytes (the reference has nothing of the
  * kind; a caller would download every frame and transform on the host).  Part of the new surface, like the meter and the

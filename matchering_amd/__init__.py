@@ -21,3 +21,4 @@ from .delivery import Delivered, Delivery, NoiseShaper, TruePeakLimiter  # noqa:
 from .qc import Audit, AuditLimits, audit  # noqa: F401  (nor this: the quality-control pass over tracks, renderings and written files)
 from .visuals import Overview, Spectrogram, Visuals, VisualsRequest, overview, spectrogram  # noqa: F401  (nor this: waveform overview and spectrogram of frames in HBM)
 from .eq import MatchingEq, ToneBand  # noqa: F401  (nor this: strength, boost / cut caps, minimum phase and tone controls for the matching EQ)
+from .repair import ClipRepair, Repaired, repair_clipping  # noqa: F401  (nor this: a clipped target's short flat tops rebuilt in HBM before it is mastered)

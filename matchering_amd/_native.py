@@ -145,6 +145,34 @@ class MgxAuditReport(ctypes.Structure):
     ]
 
 
+class MgxDeclipParams(ctypes.Structure):
+    """mgx_declip_params (include/mgx.h)."""
+
+    _fields_ = [
+        ("level", ctypes.c_double),
+        ("max_rise", ctypes.c_double),
+        ("min_run", ctypes.c_int32),
+        ("max_run", ctypes.c_int32),
+    ]
+
+
+class MgxDeclipReport(ctypes.Structure):
+    """mgx_declip_report (include/mgx.h)."""
+
+    _fields_ = [
+        ("runs_repaired", ctypes.c_int64 * 2),
+        ("samples_repaired", ctypes.c_int64 * 2),
+        ("samples_raised", ctypes.c_int64 * 2),
+        ("longest_repaired", ctypes.c_int64 * 2),
+        ("first_repaired", ctypes.c_int64 * 2),
+        ("runs_short", ctypes.c_int64 * 2),
+        ("runs_long", ctypes.c_int64 * 2),
+        ("runs_edge", ctypes.c_int64 * 2),
+        ("peak_before", ctypes.c_double * 2),
+        ("peak_after", ctypes.c_double * 2),
+    ]
+
+
 class MgxSpectrogramSpec(ctypes.Structure):
     """mgx_spectrogram_spec (include/mgx.h)."""
 
@@ -333,6 +361,10 @@ SYMBOLS = {
                                  ctypes.POINTER(MgxAuditReport), c_double_p, ctypes.c_int64, c_int64_p]),
     "mgx_audit_gate": (ctypes.c_int, [c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                       ctypes.POINTER(MgxAuditReport)]),
+    "mgx_declip_check": (ctypes.c_int, [ctypes.POINTER(MgxDeclipParams)]),
+    "mgx_declip": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxDeclipParams), _VP,
+                                  ctypes.POINTER(MgxDeclipReport)]),
+    "mgx_declip_report_read": (ctypes.c_int, [_VP, ctypes.POINTER(MgxDeclipReport)]),
     "mgx_spectrogram_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(MgxSpectrogramSpec), ctypes.POINTER(ctypes.c_int32),
                                             c_int64_p, ctypes.POINTER(ctypes.c_int32)]),
     "mgx_spectrogram": (ctypes.c_int, [_VP, _VP, ctypes.c_int64, ctypes.POINTER(MgxSpectrogramSpec),

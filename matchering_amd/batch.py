@@ -266,8 +266,9 @@ def _device_worker(device_index, lane, config, needs, master, encodings=None):
     ``encodings``: stages.main's (integer PCM renderings straight from the GPU).  ``deliveries`` (per call): a job's
     ``delivery.DeliveryRequest``, handed to ``main`` where the job has one; ``eq`` (per call): the job's
     ``eq.MatchingEq``, likewise; ``audit`` (per call): ``stages.main``'s handler, where the job asks for audits;
-    ``visuals`` (per call): the same for its pictures."""
-    def extra(deliveries, eq, audit, visuals=None):
+    ``visuals`` (per call): the same for its pictures; ``repair`` (per call): ``stages.main``'s, where the job asks for
+    its target's clipping to be repaired."""
+    def extra(deliveries, eq, audit, visuals=None, repair=None):
         given = {"deliveries": deliveries} if deliveries else {}
         if eq is not None:
             given["eq"] = eq
@@ -275,23 +276,25 @@ def _device_worker(device_index, lane, config, needs, master, encodings=None):
             given["audit"] = audit
         if visuals is not None:
             given["visuals"] = visuals
+        if repair is not None:
+            given["repair"] = repair
         return given
 
     if master is not None:                         # tests inject a stand-in for the GPU
         if encodings is None or not any(encodings):
-            return lambda pair, deliveries=None, eq=None, audit=None, visuals=None: master(pair[0], pair[1], config, *needs,
-                                                                             **extra(deliveries, eq, audit, visuals))
-        return lambda pair, deliveries=None, eq=None, audit=None, visuals=None: master(pair[0], pair[1], config, *needs, encodings=encodings,
-                                                                         **extra(deliveries, eq, audit, visuals))
+            return lambda pair, deliveries=None, eq=None, audit=None, visuals=None, repair=None: master(
+                pair[0], pair[1], config, *needs, **extra(deliveries, eq, audit, visuals, repair))
+        return lambda pair, deliveries=None, eq=None, audit=None, visuals=None, repair=None: master(
+            pair[0], pair[1], config, *needs, encodings=encodings, **extra(deliveries, eq, audit, visuals, repair))
     from .stages import main
 
     dev = lane_device(device_index, lane)
-    return lambda pair, deliveries=None, eq=None, audit=None, visuals=None: main(pair[0], pair[1], config, *needs, device=dev,
-                                                                   encodings=encodings, **extra(deliveries, eq, audit, visuals))
+    return lambda pair, deliveries=None, eq=None, audit=None, visuals=None, repair=None: main(
+        pair[0], pair[1], config, *needs, device=dev, encodings=encodings, **extra(deliveries, eq, audit, visuals, repair))
 
 
 def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
-                need_no_limiter_normalized=False, device_index=0, lanes=None, master=None, on_result=None):
+                need_no_limiter_normalized=False, device_index=0, lanes=None, master=None, on_result=None, repair=None):
     """``stages.main`` over a list of (target, reference) arrays on ONE GPU, ``lanes`` pairs in flight
     (``None``: as many as ``choose_lanes`` measures to be best on this GPU).
 
@@ -300,7 +303,11 @@ def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
     calling ``stages.main`` pair by pair: lanes only change when work is submitted, never what is
     computed.  With ``on_result(index, triple)`` every triple is handed over as it completes (from a lane
     thread) and NOT kept: the pinned host blocks the results live in are recycled as soon as the
-    consumer lets go of them, and the returned list holds ``None``."""
+    consumer lets go of them, and the returned list holds ``None``.  ``repair``: ``stages.main``'s, for every pair (a
+    handler in it is called from the lane threads)."""
+    from .repair import as_repair
+
+    as_repair(repair)                                  # (ValueError before a device is touched)
     config = config if config is not None else Config()
     needs = (need_default, need_no_limiter, need_no_limiter_normalized)
     out = [None] * len(pairs)
@@ -313,8 +320,11 @@ def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
 
     if lanes is None:
         lanes = choose_lanes(device_index, master=master) if len(pairs) > 2 else 2
-    pool = _Lanes(lambda lane: _device_worker(device_index, lane, config, needs, master),
-                  max(1, min(lanes, MAX_LANES, len(pairs) or 1)))
+    def worker_for(lane):
+        worker = _device_worker(device_index, lane, config, needs, master)
+        return worker if repair is None else (lambda pair: worker(pair, repair=repair))
+
+    pool = _Lanes(worker_for, max(1, min(lanes, MAX_LANES, len(pairs) or 1)))
     for i, pair in enumerate(pairs):
         pool.submit(i, pair, done)
     pool.close()
@@ -322,7 +332,8 @@ def master_many(pairs, config=None, need_default=True, need_no_limiter=False,
 
 
 def master_album(targets, reference, config=None, rank=None, world_size=None, device_index=None, root=0,
-                 exchange=None, need_default=True, need_no_limiter=False, need_no_limiter_normalized=False, eq=None):
+                 exchange=None, need_default=True, need_no_limiter=False, need_no_limiter_normalized=False, eq=None,
+                 repair=None):
     """Album mode across the ranks of one node: ONE matching FIR for every track.
 
     Rank ``root`` masters ``targets[0]`` against ``reference`` the ordinary way; the FIR pair it designed
@@ -332,9 +343,14 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     ``{index: triple}`` for this rank's tracks.  ``reference`` may be a ``profile.ReferenceProfile``: the reference
     is then never uploaded or analysed here (``mgx_master_with_profile``).  ``exchange(payload, size)`` must hand rank 0's 128-byte
     RCCL id to all ranks (bench.Ranks.broadcast_bytes); not needed with one rank.  ``eq`` (an ``eq.MatchingEq``) shapes
-    the album's one FIR: it applies on the rank that designs it, every other call is given the shaped taps."""
+    the album's one FIR: it applies on the rank that designs it, every other call is given the shaped taps.  ``repair``:
+    ``stages.main``'s, for every track -- the design pass hears the repaired first track too."""
     from .eq import as_eq
+    from .repair import as_repair
     from .stages import main
+
+    as_repair(repair)
+    mended = {} if repair is None else {"repair": repair}
 
     config = config if config is not None else Config()
     eq = as_eq(eq)
@@ -349,7 +365,7 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
     with dev.lock:
         fir = dev.alloc(count * 4)
         if r == root:                                           # the design pass; its result is track 0's
-            first = main(targets[0], reference, config, *needs, device=dev, eq=eq)
+            first = main(targets[0], reference, config, *needs, device=dev, eq=eq, **mended)
             taps_ptr, taps = dev.last_fir()
             assert taps == config.fft_size
             designed = dev.download(taps_ptr, (count,))
@@ -365,7 +381,7 @@ def master_album(targets, reference, config=None, rank=None, world_size=None, de
             dev.comm_destroy()
         for i in mine:
             if i not in results:
-                results[i] = main(targets[i], reference, config, *needs, device=dev, fir=fir)
+                results[i] = main(targets[i], reference, config, *needs, device=dev, fir=fir, **mended)
         fir.release()
     return results
 
@@ -488,7 +504,7 @@ class _WithDeliveries(tuple):
 
 
 def process_batch(jobs, config=None, rank=None, world_size=None, device_index=None, lanes=None, io_threads=4,
-                  master=None, share_references=False, eq=None):
+                  master=None, share_references=False, eq=None, repair=None):
     """``process`` for a list of jobs, this rank's share only.
 
     ``jobs``: dicts with "target", "reference" (paths) and "results" (list of ``Result``); in place of "reference" a
@@ -503,21 +519,26 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
     job that has no "eq" of its own (an ``eq.MatchingEq`` or the JSON object of one); what the library refuses is a
     ValueError before a file is read.  A job with ``"audit": True`` has every track, rendering and delivery audited
     (``qc.audit``; the deliveries as the integer samples their files hold) and carries the audits afterwards as plain
-    dicts under ``"audit"``, keyed "target", "reference", the renderings' names and "delivered:" + file."""
+    dicts under ``"audit"``, keyed "target", "reference", the renderings' names and "delivered:" + file.  ``repair``: the
+    ``repair.ClipRepair`` (or its JSON: True, an object) of every job that has no "repair" of its own (``"repair": False`` on a job: none,
+    whatever the batch's); a job that is
+    repaired carries the ``Repaired`` of its target afterwards as a plain dict under ``"repaired"``."""
     from .delivery import DeliveryRequest, renderings_wanted, write_results
     from .eq import as_eq
+    from .repair import as_repair
 
     config = config if config is not None else Config()
     r, w, local = rank_and_world(rank, world_size)
     mine = shard(jobs, r, w)
     eq = as_eq(eq)
-    eqs = {}
+    eqs, repairs = {}, {}
     for i in mine:
         if not jobs[i].get("results"):
             raise RuntimeError("The result list is empty")
         eqs[i] = as_eq(jobs[i]["eq"]) if jobs[i].get("eq") is not None else eq
         if eqs[i] is not None:
             eqs[i].check(config)
+        repairs[i] = as_repair(jobs[i]["repair"] if jobs[i].get("repair") is not None else repair)
         # (a delivery rate the device converter refuses is a ValueError here, before a file is read)
         DeliveryRequest.for_results(jobs[i]["results"]).check_rates(config.internal_sample_rate)
     device_index = local if device_index is None else device_index
@@ -592,6 +613,13 @@ def process_batch(jobs, config=None, rank=None, world_size=None, device_index=No
                     pictures, sizes = {}, VisualsRequest.from_json(jobs[index]["visuals"])
                     jobs[index]["visuals"] = pictures
                     shaped["visuals"] = (lambda name, value, kept=pictures: kept.__setitem__(name, value.as_dict()), sizes)
+                handler, mend = repairs[index]
+                if mend is not None:
+                    def mended(name, value, job=jobs[index], also=handler):
+                        job["repaired"] = value.as_dict()
+                        if also is not None:
+                            also(name, value)
+                    shaped["repair"] = (mended, mend)
                 if not deliveries:
                     return workers[key]((target, reference), **shaped)
                 return _WithDeliveries(workers[key]((target, reference), deliveries, **shaped), deliveries)
@@ -654,6 +682,12 @@ def jobs_from_json(path):
             job["audit"] = True
         if item.get("visuals"):
             job["visuals"] = item["visuals"]
+        if item.get("repair") is False:
+            job["repair"] = False                  # (the job opts out of a batch-wide ``repair=``)
+        elif item.get("repair") is not None:
+            from .repair import ClipRepair
+
+            job["repair"] = ClipRepair.from_json(item["repair"]).check()
         if item.get("eq") is not None:
             from .eq import MatchingEq
 

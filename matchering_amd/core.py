@@ -59,7 +59,7 @@ def _same_file(a, b):
 
 def process(target: str, reference: str, results: list, config: Config = None,
             preview_target: Result = None, preview_result: Result = None, loudness=None, eq=None, audit=None,
-            visuals=None):
+            visuals=None, repair=None):
     # (``loudness``: no counterpart in the reference -- a callable that receives (name, loudness.Loudness) for "target",
     # for "reference" when its audio was loaded, and for each rendering the results need ("result", "result_no_limiter",
     # "result_no_limiter_normalized"), measured on the frames in HBM; None: nothing is measured, nothing else changes.
@@ -69,13 +69,19 @@ def process(target: str, reference: str, results: list, config: Config = None,
     # integer samples a delivery writes, read in HBM before they are downloaded; None: nothing is launched.
     # ``visuals``: a callable, or a pair (callable, visuals.VisualsRequest) giving the sizes, that receives (name,
     # visuals.Visuals) -- waveform overview and spectrogram of the frames in HBM -- for "target", "reference" and each
-    # rendering; None: nothing is launched.)
+    # rendering; None: nothing is launched.
+    # ``repair``: a repair.ClipRepair, its JSON (True or an object), or a pair (callable, ClipRepair) whose callable receives
+    # ("target", repair.Repaired) -- the target's short runs at the rail are rebuilt in HBM before it is mastered, and
+    # everything downstream hears the repaired frames.  What the library refuses is a ValueError before a file is read.
+    # None: nothing is launched.)
     from .eq import as_eq
+    from .repair import as_repair
 
     config = Config() if config is None else config
     eq = as_eq(eq)
     if eq is not None:
         eq.check(config)
+    as_repair(repair)
     debug("matchering_amd: the MI355X path behind the API of https://github.com/sergree/matchering")
     debug_line()
     info(Code.INFO_LOADING)
@@ -120,6 +126,8 @@ def process(target: str, reference: str, results: list, config: Config = None,
         extra["audit"] = audit
     if visuals is not None:
         extra["visuals"] = visuals
+    if repair is not None:
+        extra["repair"] = repair
     # (main releases the resident frames)
     renderings = main(target_track.for_main, reference_audio, config, *needs, encodings=encodings, **extra)
     del reference_audio

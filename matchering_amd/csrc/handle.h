@@ -166,6 +166,8 @@ struct mgx_handle {
     DevBuf loudness_out;                    // [nsub][2] sub-block energies, then [workgroups][2] peaks
     DevBuf tp_plane, tp_words;              // mgx_tp_limit: the d0 plane [tiles * T] float32; aggregates and peaks, [2][tiles] float64
     DevBuf audit_work, audit_out;           // mgx_audit: the segments' records and sub-block shares; the totals, then [count][3] sub-block sums
+    DevBuf declip_work, declip_out;         // mgx_declip: the segments' counters, [segments][2][DECLIP_SLOTS] int; the track's, as long long
+    bool declip_ran = false;                // declip_out holds the counters of the most recent mgx_declip call (mgx_declip_report_read)
     // mgx_spectrogram: the float32 window of every transform length this handle has drawn, built once per log2, and the
     // float64 sum of its values
     struct SpectroWindow {

@@ -33,6 +33,7 @@
 #include "audit_kernel.h"
 #include "visuals_kernel.h"
 #include "eq_tone_kernels.h"           // (last: only a call with a tone launches it, and it moves no other kernel)
+#include "declip_kernel.h"             // (behind it: only mgx_declip launches it)
 
 #include "mgx_policy.h"
 #include "handle.h"
@@ -496,6 +497,73 @@ int mgx_audit(mgx_handle* h, const void* x_dev, int64_t n_frames, int32_t bits, 
     report->gap_longest = t->gap_longest, report->gap_at = t->gap_at;
     if (sub_sums) std::memcpy(sub_sums, sums, (size_t)subs * 3 * sizeof(double));
     return audit_gate(sums, subs, n_frames, B, report);
+}
+
+int mgx_declip(mgx_handle* h, const float* x_dev, int64_t n_frames, const mgx_declip_params* params, float* out_dev,
+               mgx_declip_report* report) {
+    // everything that depends on the numbers alone is settled before the handle is touched
+    static_assert(DECLIP_MAX_RUN == MGX_DECLIP_MAX_RUN, "mgx_declip_check refuses what the kernel's halo does not hold");
+    MGX_TRY(mgx_declip_check(params));
+    if (n_frames < 0) return fail(MGX_ERR_ARGUMENT, "n_frames: negative");
+    if (n_frames > LOUD_FRAMES_MAX) return fail(MGX_ERR_UNSUPPORTED, "mgx_declip: tracks of more than 500 million frames are not repaired here");
+    if (!h) return fail(MGX_ERR_ARGUMENT, "h: null handle");
+    if (!x_dev) return fail(MGX_ERR_ARGUMENT, "x_dev: null");
+    if (!out_dev) return fail(MGX_ERR_ARGUMENT, "out_dev: null");
+    if (((size_t)x_dev) & 15) return fail(MGX_ERR_ARGUMENT, "x_dev: must be 16-byte aligned");
+    if (((size_t)out_dev) & 15) return fail(MGX_ERR_ARGUMENT, "out_dev: must be 16-byte aligned");
+    const char* xb = (const char*)x_dev;
+    const char* ob = (const char*)out_dev;
+    if (xb < ob + (size_t)n_frames * 8 && ob < xb + (size_t)n_frames * 8) return fail(MGX_ERR_ARGUMENT, "out_dev: overlaps x_dev");
+    if (report) {
+        std::memset(report, 0, sizeof(*report));
+        report->first_repaired[0] = report->first_repaired[1] = -1;
+    }
+    if (n_frames == 0) {
+        h->declip_ran = false;
+        return 0;
+    }
+    MGX_TRY(open_main(h));
+    DeclipArgs a;
+    declip_launch(a, n_frames, params->level, params->max_rise, params->min_run, params->max_run);
+    MGX_TRY(ensure(h, h->declip_work, declip_seg_bytes(a)));
+    MGX_TRY(ensure(h, h->declip_out, DECLIP_TOTALS_BYTES));
+    a.x = x_dev;
+    a.out = out_dev;
+    a.seg = (int*)h->declip_work.p;
+    a.totals = (long long*)h->declip_out.p;
+    hipLaunchKernelGGL(k_declip<0>, dim3((unsigned)a.segments), dim3(DECLIP_THREADS), 0, h->stream, a);
+    hipLaunchKernelGGL(k_declip_fold<0>, dim3(1), dim3(DECLIP_FOLD_THREADS), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    h->declip_ran = true;
+    return report ? mgx_declip_report_read(h, report) : 0;
+}
+
+int mgx_declip_report_read(mgx_handle* h, mgx_declip_report* report) {
+    if (!h) return fail(MGX_ERR_ARGUMENT, "h: null handle");
+    if (!report) return fail(MGX_ERR_ARGUMENT, "report: null");
+    std::memset(report, 0, sizeof(*report));
+    report->first_repaired[0] = report->first_repaired[1] = -1;
+    if (!h->declip_ran) return 0;                               // (no call yet, or the last one had no frames)
+    HIP_TRY(hipSetDevice(h->device));
+    MGX_TRY(ensure_pinned(h, (size_t)1 << 16));
+    HIP_TRY(hipMemcpyAsync(h->pinned, h->declip_out.p, DECLIP_TOTALS_BYTES, hipMemcpyDeviceToHost, h->stream));
+    MGX_TRY(sync_main(h));
+    MGX_TRY(check_device_error(h));
+    const long long* t = (const long long*)h->pinned;
+    for (int c = 0; c < 2; ++c) {
+        const long long* v = t + c * DECLIP_SLOTS;
+        report->runs_repaired[c] = v[DECLIP_RUNS_REPAIRED], report->samples_repaired[c] = v[DECLIP_SAMPLES_REPAIRED];
+        report->samples_raised[c] = v[DECLIP_SAMPLES_RAISED], report->longest_repaired[c] = v[DECLIP_LONGEST];
+        report->first_repaired[c] = v[DECLIP_FIRST];
+        report->runs_short[c] = v[DECLIP_RUNS_SHORT], report->runs_long[c] = v[DECLIP_RUNS_LONG], report->runs_edge[c] = v[DECLIP_RUNS_EDGE];
+        const unsigned before = (unsigned)v[DECLIP_PEAK_BEFORE], after = (unsigned)v[DECLIP_PEAK_AFTER];
+        float f;
+        std::memcpy(&f, &before, 4);
+        report->peak_before[c] = (double)f;
+        std::memcpy(&f, &after, 4);
+        report->peak_after[c] = (double)f;
+    }
+    return 0;
 }
 
 int mgx_spectrogram(mgx_handle* h, const float* x_dev, int64_t n_frames, const mgx_spectrogram_spec* spec,

@@ -604,6 +604,16 @@ int mgx_audit_gate(const double* sub_sums, int64_t count, int64_t n_frames, int3
     return audit_gate(sub_sums, count, n_frames, B, report);
 }
 
+int mgx_declip_check(const mgx_declip_params* params) {
+    if (!params) return fail(MGX_ERR_ARGUMENT, "params: null");
+    if (!std::isfinite(params->level) || params->level <= 0.0) return fail(MGX_ERR_ARGUMENT, "level: must be finite and positive");
+    if (!std::isfinite(params->max_rise) || params->max_rise < 1.0) return fail(MGX_ERR_ARGUMENT, "max_rise: must be finite and at least 1");
+    if (params->min_run < 1) return fail(MGX_ERR_ARGUMENT, "min_run: below 1");
+    if (params->max_run < params->min_run || params->max_run > MGX_DECLIP_MAX_RUN)
+        return fail(MGX_ERR_ARGUMENT, "max_run: outside [min_run, " + std::to_string(MGX_DECLIP_MAX_RUN) + "]");
+    return 0;
+}
+
 int mgx_spectrogram_plan(int64_t n_frames, const mgx_spectrogram_spec* spec, const int32_t* edges, int64_t* hops,
                          int32_t* columns) {
     SpectroPlan plan;

@@ -458,6 +458,30 @@ class Device:
         value = from_report(report, rate)
         return (value, sums) if sub_sums else value
 
+    def declip(self, buf, frames, params, report=True):
+        """Clip repair of (frames, 2) float32 in HBM (``mgx_declip``): ``params`` is a ``_native.MgxDeclipParams``.
+        Returns ``(out, report)``: the repaired frames in a new DeviceBuffer and the ``_native.MgxDeclipReport``, for
+        which the call waits; with ``report=False`` it is only queued and the second value is None."""
+        ptr = buf.ptr if hasattr(buf, "ptr") else buf.buf.ptr
+        made = DeviceBuffer(self, max(int(frames) * 8, 1))
+        found = _native.MgxDeclipReport() if report else None
+        try:
+            check(library().mgx_declip(self.handle, ctypes.c_void_p(ptr), int(frames), ctypes.byref(params),
+                                       ctypes.c_void_p(made.ptr), ctypes.byref(found) if report else None))
+        except Exception:
+            made.release()
+            raise
+        if report and frames > 0:
+            self._keep_until_sync.clear()      # (the call has waited for the stream)
+        return made, found
+
+    def declip_report(self):
+        """The report of the most recent ``declip`` of this device, for one queued with ``report=False``
+        (``mgx_declip_report_read``); waits for the stream."""
+        found = _native.MgxDeclipReport()
+        check(library().mgx_declip_report_read(self.handle, ctypes.byref(found)))
+        return found
+
     def overview(self, buf, frames, rate, columns):
         """The waveform overview of (frames, 2) float32 in HBM (``mgx_overview``): a ``visuals.Overview`` of ``columns``
         columns."""

@@ -77,7 +77,7 @@ def _limited(dev, rendering, n, rate, delivery, bits, measured):
 
 def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default: bool = True,
          need_no_limiter: bool = False, need_no_limiter_normalized: bool = False, device=None, fir=None,
-         encodings=None, preview=None, loudness=None, deliveries=None, eq=None, audit=None, visuals=None):
+         encodings=None, preview=None, loudness=None, deliveries=None, eq=None, audit=None, visuals=None, repair=None):
     # (``device``: the handle to run on, default the process-wide one; ``fir``: a DeviceBuffer with a
     # matching FIR to apply instead of designing one -- batch.master_album; ``encodings``: per output,
     # None for float32 frames or "PCM_16" / "PCM_24" / "PCM_32" for the integer samples a file of that
@@ -106,9 +106,20 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
     # nothing is launched.
     # ``visuals``: a callable, or a pair (callable, visuals.VisualsRequest) giving the sizes, that receives (name,
     # visuals.Visuals) -- the waveform overview and the spectrogram (mgx_overview, mgx_spectrogram) of the float frames
-    # in HBM -- for the names ``audit`` receives for float frames.  None: nothing is launched.)
+    # in HBM -- for the names ``audit`` receives for float frames.  None: nothing is launched.
+    # ``repair``: a repair.ClipRepair, its JSON (True or an object), or a pair (callable, ClipRepair) whose callable
+    # receives ("target", repair.Repaired) -- the target's short runs at the rail are rebuilt (mgx_declip) into a NEW buffer
+    # right after upload, and that buffer is what the master step sees on every route (plain, ``eq``, ``fir``, a profile),
+    # what the "target" callbacks of ``loudness`` / ``audit`` / ``visuals`` measure and what the target's preview is cut
+    # from; the frames the caller handed in are not written (resident ``DeviceFrames`` are released at the end, as they
+    # are without a repair; the new buffer is released with the outputs, on error too).  The repair is queued in front
+    # of the master call and its report read behind it, where main has waited anyway: an explicit ``level`` adds no wait;
+    # with ``level=None``, the default, the level comes from the track's own peak (Device.peak_count), which does wait
+    # once in front of the master call.  None or False: nothing is launched.)
     from .eq import as_eq
+    from .repair import as_repair
 
+    notify_repair, repair = as_repair(repair)                # (ValueError before anything reaches the GPU)
     eq = as_eq(eq)
     if eq is not None:
         eq.check(config)                                     # (ValueError before anything reaches the GPU)
@@ -140,11 +151,23 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
         returned = (need_default, need_no_limiter, need_no_limiter_normalized)
         cut = deliveries.needs() if deliveries else (False, False, False)
         outs = [dev.alloc(n * 8) if need or extra else None for need, extra in zip(returned, cut)]
+        uploaded, fixed = t_dev, None
         try:
+            if repair is not None:
+                from .repair import finish, queue
+
+                fixed, rail = queue(dev, t_dev, n, repair)
+                if fixed is not None:
+                    t_dev = fixed                                # (from here on "the target" is the repaired buffer)
             route = {} if p_dev is None else {"profile": p_dev}
             if eq is not None:
                 route["eq"] = eq
             report = dev.master(t_dev, n, r_dev, nr, native, *outs, fir=fir, **route)
+            if repair is not None:
+                found = finish(dev, fixed, rail, n)
+                debug(found.describe())
+                if notify_repair is not None:
+                    notify_repair("target", found)
             debug(f"target: {report.target_divisions} pieces of {report.target_piece} frames, "
                   f"{report.target_loud_count} of them loud; reference: {report.reference_divisions} pieces of "
                   f"{report.reference_piece} frames, {report.reference_loud_count} loud")
@@ -274,7 +297,7 @@ def main(target: np.ndarray, reference: np.ndarray, config: Config, need_default
                 if piece is not None:
                     piece.release()
         finally:
-            for b in (t_dev, r_dev, *outs):
+            for b in (uploaded, fixed, r_dev, *outs):
                 if b is not None:
                     b.release()
     return results
